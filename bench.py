@@ -1,20 +1,25 @@
 """DMA-YOLO hot-path benchmark (BASELINE.json metric: training images/s fwd+bwd @640 & @1536, detect p50 ms incl.
 NMS, 1/2/4/8 GPUs).
 
-python bench.py --gpus N --steps K --warmup W [--config dma-1536|v5s-640|...] [--also v5s-640|none]
+python bench.py --gpus N --steps K --warmup W [--config dma-1536|v5s-640|...] [--dump-outputs DIR]
+                [--full [--also v5s-640|none]]
 
-The headline line is DMA-YOLO-l @1536 (BASELINE configs[2]; configs[3] at N = 8), the north-star model; the same
-measurement on yolov5s @640 bs64 (configs[1]) rides in the same JSON line under "at_640" so one default run covers
-both halves of the metric.  `--gpus N` without a torchrun environment re-launches itself as N ranks
-(torch.distributed.run as a child process; this parent never touches the GPU).
+The headline line is DMA-YOLO-l @1536 (BASELINE configs[2]; configs[3] at N = 8), the north-star model.  A plain run
+does only what that figure needs: build the model, W warmup steps, K timed steps, the JSON line.  `--full` adds
+everything else to the same line: the roofline pass, detect p50 and NMS under load, the CPU oracle baseline, and the
+same measurement on the `--also` configurations (yolov5s @640 bs64, configs[1], under "at_640", so one `--full` run
+covers both halves of the metric).  `--dump-outputs DIR` writes what the last timed step left with its caller as
+DIR/<name>.npy (see `snapshot_outputs`); the inputs are seeded, so two builds can be compared array for array.
+`--gpus N` without a torchrun environment re-launches itself as N ranks (torch.distributed.run as a child process;
+this parent never touches the GPU).
 
 One timed step = one iteration of the reference's batch loop (train.py:400-454) through dmayolo.trainer.Trainer on a
 pre-staged synthetic VisDrone-shaped batch: uint8 -> /255 -> forward -> ComputeLoss (SIoU) -> backward seeded with
 loss-scale * WORLD_SIZE (DDP all-reduce over RCCL when N > 1) -> GradScaler step (SGD-nesterov, warmup lr/momentum,
 accumulate) -> EMA (rank 0).  value = images/s over all ranks (max-over-ranks time), scaling weak (per-GPU batch
-fixed).  Also reported: the roofline of the dominant conv kernel family from live HIP events, detect p50 (bs1,
-uint8 -> forward -> NMS) and NMS under a 2,000-candidate load, and the CPU oracle (`cpu_baseline`, kind "port") on a
-bounded sample.
+fixed).  With `--full`, also reported: the roofline of the dominant conv kernel family from live HIP events, detect
+p50 (bs1, uint8 -> forward -> NMS) and NMS under a 2,000-candidate load, and the CPU oracle (`cpu_baseline`, kind
+"port") on a bounded sample.
 """
 import argparse
 import gc
@@ -55,18 +60,24 @@ def parse():
     ap.add_argument('--steps', type=int, default=10)
     ap.add_argument('--warmup', type=int, default=3)
     ap.add_argument('--config', default='dma-1536', choices=list(CONFIGS))
+    ap.add_argument('--full', action='store_true',
+                    help='besides the timed steps of --config: the roofline pass, detect p50 / NMS under load, the CPU '
+                         'baseline and the --also configurations (a plain run measures the headline figure only)')
+    ap.add_argument('--dump-outputs', default='', metavar='DIR',
+                    help='after the timed steps write what the last one computed (loss, loss items, a seeded sample '
+                         'of the updated model / EMA state) as DIR/<name>.npy, float32')
     ap.add_argument('--also', default='v5s-640,c5-1920',
-                    help='comma list of further configurations measured in the same run, each nested in the JSON '
-                         'line as at_<img> ("none": only --config).  c5-1920 (BASELINE configs[4]) runs with the fp8 '
+                    help='with --full: comma list of further configurations measured in the same run, each nested in '
+                         'the JSON line as at_<img> ("none": only --config).  c5-1920 (BASELINE configs[4]) runs with the fp8 '
                          'forward, plus a bf16 run of the same steps for its step time')
     ap.add_argument('--batch', type=int, default=0, help='per-GPU batch of --config (default: the config)')
     ap.add_argument('--dtype', default='bf16', choices=['bf16', 'fp32'])
     ap.add_argument('--no-cpu-baseline', action='store_true')
     ap.add_argument('--no-detect', action='store_true')
     ap.add_argument('--cpu-seconds', type=float, default=15.0)
-    ap.add_argument('--layer-report', action='store_true', help='per-conv-shape timing table on stderr')
-    ap.add_argument('--launch-table', default='', help='CSV of every timed conv launch of the roofline pass (kind, '
-                    'shape, algorithmic flops / bytes, measured us, roofline us): the table behind roofline.frac')
+    ap.add_argument('--layer-report', action='store_true', help='with --full: per-conv-shape timing table on stderr')
+    ap.add_argument('--launch-table', default='', help='with --full: CSV of every timed conv launch of the roofline '
+                    'pass (kind, shape, algorithmic flops / bytes, measured us, roofline us): the table behind roofline.frac')
     ap.add_argument('--fp8', action='store_true',
                     help='config 5 (BASELINE configs[4]): e4m3 MFMA forward for every conv with C %% 128 == 0')
     ap.add_argument('--ddp', default='arena', choices=['arena', 'torch'],
@@ -77,7 +88,10 @@ def parse():
                     help='ArenaDDP: send the gradient buckets as bf16 (DDP bf16_compress_hook semantics)')
     ap.add_argument('--backend', default='nccl', choices=['nccl', 'gloo'],
                     help='process-group backend (nccl = RCCL; gloo only to rehearse several ranks on one GPU)')
-    return ap.parse_args()
+    a = ap.parse_args()
+    if (a.layer_report or a.launch_table) and not a.full:
+        ap.error('--layer-report / --launch-table read the roofline pass: add --full')
+    return a
 
 
 def _free_port():
@@ -281,9 +295,38 @@ def roofline(ks, steps, el_events, dtype, cfg_name):
                             % (steps, el_events * 1e3 / steps))
 
 
+SAMPLE = 1 << 21  # elements kept of each dumped state vector (8 MB as float32)
+
+
+def snapshot_outputs(tr, loss, items):
+    """What a caller of Trainer.step holds after the last timed step: the returned loss [1] and loss items [3], and the
+    state the step updated in place -- the floating-point state_dict entries (weights, BN running statistics) of the
+    model and of its EMA, each flattened in state_dict order into one vector of which a fixed sample (SAMPLE sorted
+    indices drawn with seed 0) is kept.  float32 numpy arrays by name."""
+    import numpy as np
+    out = {'loss': loss.detach().float().reshape(-1).cpu().numpy(),
+           'loss_items': items.detach().float().reshape(-1).cpu().numpy()}
+    for key, m in (('model_state', tr.model), ('ema_state', tr.ema.ema if tr.ema is not None else None)):
+        if m is None:
+            continue
+        flat = torch.cat([v.detach().float().reshape(-1) for v in m.state_dict().values() if v.dtype.is_floating_point])
+        if flat.numel() > SAMPLE:
+            idx = np.sort(np.random.default_rng(0).integers(0, flat.numel(), SAMPLE))
+            flat = flat[torch.from_numpy(idx).to(flat.device)]
+        out[key] = flat.cpu().numpy()
+    return out
+
+
+def write_outputs(path, arrays):
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    for k, v in arrays.items():
+        np.save(os.path.join(path, k + '.npy'), v.astype(np.float32, copy=False))
+
+
 def run_config(name, a, world, rank, dev_idx, device, dtype, batch=0, cpu_seconds=15.0, fp8=False, light=False):
     """light: only the timed steps (no roofline pass, detect or CPU baseline) -- the bf16 twin of the fp8 config-5
-    leg, for its step time"""
+    leg, for its step time.  Without --full every run is the timed steps alone."""
     from dmayolo.functional import KernelTimer
     from dmayolo.synthetic import images, targets, clustered_predictions
     from dmayolo.infer import GraphedDetector
@@ -336,29 +379,33 @@ def run_config(name, a, world, rank, dev_idx, device, dtype, batch=0, cpu_second
         gc.collect()
         torch.cuda.empty_cache()
         return res
-    # roofline pass: the same K steps again with a HIP event pair around every implicit-GEMM launch on its stream
-    # (functional.KernelTimer).  Kept out of the timed region: ~380 event records per yolov5s step cost ~6 % of the
-    # step (3400 vs 3184 img/s measured), which would understate `value`.
-    KernelTimer.enabled = True
-    KernelTimer.records = []
-    t1 = time.perf_counter()
-    for _ in range(a.steps):
-        tr.step(imgs, tg)
-    torch.cuda.synchronize()
-    el_events = time.perf_counter() - t1
-    KernelTimer.enabled = False
-    detail = {} if a.layer_report else None
-    table = [] if a.launch_table else None
-    ks = KernelTimer.summary(detail, PEAK_FLOPS[dtype], PEAK_BW, peak_flops_f8=PEAK_FLOPS['fp8'], table=table)
-    if table is not None and rank == 0:
-        write_launch_table(a.launch_table if name == a.config else a.launch_table.replace('.csv', f'_{name}.csv'),
-                           table, ks, name)
-    if detail and rank == 0:
-        tot = sum(v[2] for v in detail.values())
-        print(f'[{name}] kind        N    C    H    W    K  k s  launches  ms/step  TFLOP/s  share', file=sys.stderr)
-        for (kind, tag), v in sorted(detail.items(), key=lambda kv: -kv[1][2]):
-            print('%-10s %s %6d %8.3f %8.1f %6.3f' % (kind, ' '.join('%4d' % t for t in tag), v[0],
-                  v[2] * 1e3 / a.steps, v[1] / v[2] / 1e12, v[2] / tot), file=sys.stderr)
+    if a.dump_outputs and name == a.config and rank == 0:  # before any further step moves the state on
+        write_outputs(a.dump_outputs, snapshot_outputs(tr, loss, items))
+    ks = None
+    if a.full:
+        # roofline pass: the same K steps again with a HIP event pair around every implicit-GEMM launch on its stream
+        # (functional.KernelTimer).  Kept out of the timed region: ~380 event records per yolov5s step cost ~6 % of the
+        # step (3400 vs 3184 img/s measured), which would understate `value`.
+        KernelTimer.enabled = True
+        KernelTimer.records = []
+        t1 = time.perf_counter()
+        for _ in range(a.steps):
+            tr.step(imgs, tg)
+        torch.cuda.synchronize()
+        el_events = time.perf_counter() - t1
+        KernelTimer.enabled = False
+        detail = {} if a.layer_report else None
+        table = [] if a.launch_table else None
+        ks = KernelTimer.summary(detail, PEAK_FLOPS[dtype], PEAK_BW, peak_flops_f8=PEAK_FLOPS['fp8'], table=table)
+        if table is not None and rank == 0:
+            write_launch_table(a.launch_table if name == a.config else a.launch_table.replace('.csv', f'_{name}.csv'),
+                               table, ks, name)
+        if detail and rank == 0:
+            tot = sum(v[2] for v in detail.values())
+            print(f'[{name}] kind        N    C    H    W    K  k s  launches  ms/step  TFLOP/s  share', file=sys.stderr)
+            for (kind, tag), v in sorted(detail.items(), key=lambda kv: -kv[1][2]):
+                print('%-10s %s %6d %8.3f %8.1f %6.3f' % (kind, ' '.join('%4d' % t for t in tag), v[0],
+                      v[2] * 1e3 / a.steps, v[1] / v[2] / 1e12, v[2] / tot), file=sys.stderr)
     if world > 1:
         t = torch.tensor([el], device=device)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -370,11 +417,11 @@ def run_config(name, a, world, rank, dev_idx, device, dtype, batch=0, cpu_second
                        **({'grad_exchange': (a.ddp + ('' if a.ddp == 'torch' else ' bucket %g MB' % a.bucket_mb) +
                                              ('' if a.grad_compress == 'none' else ' ' + a.grad_compress))}
                           if world > 1 else {})},
-               roofline=roofline(ks, a.steps, el_events, dtype, name),
+               roofline=roofline(ks, a.steps, el_events, dtype, name) if ks is not None else None,
                loss_items=[round(float(v), 5) for v in items], lr=[round(float(g['lr']), 8) for g in tr.optimizer.param_groups],
                loss_scale=tr.scaler.get_scale())
 
-    if rank == 0 and not a.no_detect:
+    if a.full and rank == 0 and not a.no_detect:
         # detect p50 (detect.py:175-243): bs1 uint8 on device -> forward -> NMS(0.25, 0.45, max_det 1000)
         ev = tr.ema.ema if tr.ema is not None else model
         ev.eval()
@@ -434,7 +481,7 @@ def run_config(name, a, world, rank, dev_idx, device, dtype, batch=0, cpu_second
     gc.collect()
     torch.cuda.empty_cache()
     res['cpu_baseline'] = None
-    if rank == 0 and world == 1 and not a.no_cpu_baseline:
+    if a.full and rank == 0 and world == 1 and not a.no_cpu_baseline:
         res['cpu_baseline'] = cpu_baseline(cfg, cpu_seconds)
     return res
 
@@ -459,7 +506,7 @@ def main():
 
     head = run_config(a.config, a, world, rank, dev_idx, device, dtype, a.batch, a.cpu_seconds, fp8=a.fp8)
     also = {}
-    for name in [n for n in a.also.split(',') if n and n != 'none' and n != a.config]:
+    for name in [n for n in a.also.split(',') if a.full and n and n != 'none' and n != a.config]:
         assert name in CONFIGS, (name, list(CONFIGS))
         f8 = name == 'c5-1920' and dtype == torch.bfloat16  # BASELINE configs[4]: "fp8 MFMA conv"
         r = run_config(name, a, world, rank, dev_idx, device, dtype, 0, a.cpu_seconds, fp8=f8)

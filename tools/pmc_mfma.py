@@ -8,7 +8,7 @@ and per family the time-weighted mean over its dispatches (= sum MFMA-busy cycle
 bench.py's roofline (tools/pmc_traffic.family), plus 'conv_3x3': every dispatch of a kernel that only runs k > 1
 layers (implicit-GEMM tiles with P1 = false, the halo kernel, the tap-fused weight-grad, the stride-2 data-grad) --
 the north-star's ">= 40 % MFMA on 3x3 implicit-GEMM" is read off that row.  Writes {config: {family: {...}}} into
-profiles/pmc_mfma.json, which bench.py copies into roofline.kernels[family].mfma_busy.
+profiles/pmc_mfma.json, which `bench.py --full` copies into roofline.kernels[family].mfma_busy.
 """
 import json
 import os

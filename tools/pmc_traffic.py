@@ -1,4 +1,5 @@
-"""HBM bytes per call of each conv kernel family from rocprofv3 --pmc passes of a bench command.
+"""HBM bytes per call of each conv kernel family from rocprofv3 --pmc passes of a `bench.py --full` command (the
+roofline pass behind --full supplies the per-family call counts read here).
 
 python tools/pmc_traffic.py <config> gpurun_out/pmc_<tag>      (reads <prefix>_fetch, <prefix>_write, and the bench
                                                                 JSON line the profiled command printed, <prefix>_fetch.log)
@@ -83,6 +84,8 @@ def bench_line(path):
 
 def main(config, prefix):
     b = bench_line(prefix + '_fetch.log')
+    if not b.get('roofline'):
+        raise SystemExit(f'{prefix}_fetch.log: the bench line has no roofline (profile `bench.py --full`)')
     steps, warm = b['steps'], b['warmup']
     nsteps = warm + 2 * steps
     kern = b['roofline']['kernels']
@@ -116,7 +119,7 @@ def main(config, prefix):
                     'pmc_over_algorithmic': pmc_step / alg_step if alg_step else None,
                     'avg_call_us_profiled': r['ns'] / calls / 1e3,
                     'source': os.path.basename(prefix) + '_{fetch,write} (rocprofv3 --kernel-trace --pmc FETCH_SIZE / '
-                              f'WRITE_SIZE; bench.py --steps {steps} --warmup {warm}: {nsteps} training steps)'}
+                              f'WRITE_SIZE; bench.py --full --steps {steps} --warmup {warm}: {nsteps} training steps)'}
     out['_per_step'] = {'pmc_bytes': tot_pmc, 'algorithmic_bytes': tot_alg,
                         'pmc_over_algorithmic': tot_pmc / tot_alg if tot_alg else None,
                         'families': sorted(k for k in out if not k.startswith('_'))}
