@@ -97,6 +97,58 @@ __global__ void decode_levels_kernel(DecTab tab, int N, int na, int no, const fl
   }
 }
 
+// one test-time-augmentation pass (models/yolo.py:199-209): decode_levels_kernel over the kept levels only (tab holds
+// them compacted, lvl[] their Detect index for the anchors, zoff[] already includes the pass's row offset), then
+// _descale_pred's in-place ops on the box columns: xywh / scale (IEEE division, the bits of torch's `/=`), then
+// x = img_w - x (flip 3) or y = img_h - y (flip 2)
+struct TtaTab {
+  DecTab t;
+  int lvl[kDecLevels];
+};
+
+template <typename T>
+__global__ void decode_tta_kernel(TtaTab tt, int N, int na, int no, const float* __restrict__ anchors,
+                                  float* __restrict__ z, long ztotal, float scale, int flip, float img_h, float img_w) {
+  const DecTab& tab = tt.t;
+  for (long g = blockIdx.x * (long)blockDim.x + threadIdx.x; g < tab.cum[tab.nl]; g += (long)gridDim.x * blockDim.x) {
+    int L = 0;
+#pragma unroll
+    for (int l = 1; l < kDecLevels; ++l)
+      if (l < tab.nl && g >= tab.cum[l]) L = l;
+    const long i = g - tab.cum[L];
+    const int H = tab.H[L], W = tab.W[L];
+    const int c = (int)(i % no);
+    long t = i / no;
+    const int w = (int)(t % W);
+    t /= W;
+    const int h = (int)(t % H);
+    t /= H;
+    const int a = (int)(t % na);
+    const int b = (int)(t / na);
+    const T* y = static_cast<const T*>(tab.y[L]);
+    const float v = to_f(y[b * tab.sb[L] + h * tab.sh[L] + w * tab.sw[L] + a * no + c]);
+    const float stride = tab.stride[L];
+    float s = 1.0f / (1.0f + expf(-v));
+    float o;
+    if (c < 2) {
+      const float gg = (float)(c == 0 ? w : h);
+      o = (s * 2.0f - 0.5f + gg) * stride;
+    } else if (c < 4) {
+      const float ag = anchors[(tt.lvl[L] * na + a) * 2 + (c - 2)] * stride;
+      const float q = s * 2.0f;
+      o = (q * q) * ag;
+    } else {
+      o = s;
+    }
+    if (c < 4) {
+      o = o / scale;  // correctly rounded (hipcc's default fp32 division); a quotient cannot contract into the subtract
+      if (c == 0 && flip == 3) o = img_w - o;
+      if (c == 1 && flip == 2) o = img_h - o;
+    }
+    z[((long)b * ztotal + tab.zoff[L] + ((long)a * H + h) * W + w) * no + c] = o;
+  }
+}
+
 // ---------------------------------------------------------------- build_targets
 struct TgtOut {
   int* b; int* a; int* gj; int* gi; int* tcls; float* tbox; float* anch; int* count;
@@ -440,6 +492,41 @@ DMY_API int dmy_detect_decode_levels(int dtype, int nl, const void* const* ys, c
   const int g = grid_cap(ceil_div(tab.cum[nl], 256), 8192);
   if (dtype) decode_levels_kernel<bf16><<<g, 256, 0, (hipStream_t)stream>>>(tab, N, na, no, anchors, z, ztotal);
   else decode_levels_kernel<float><<<g, 256, 0, (hipStream_t)stream>>>(tab, N, na, no, anchors, z, ztotal);
+  return (int)hipGetLastError();
+}
+
+DMY_API int dmy_detect_decode_tta(int dtype, int nl, const void* const* ys, const long* strides, const int* hw,
+                                  const float* lvl_stride, int N, int na, int no, const float* anchors, float* z,
+                                  long ztotal, float scale, int flip, float img_h, float img_w, int level_mask,
+                                  long zoff, void* stream) {
+  if (nl < 1 || nl > kDecLevels || !(scale > 0.f) || (flip != 0 && flip != 2 && flip != 3) || zoff < 0)
+    return (int)hipErrorInvalidValue;
+  TtaTab tt{};
+  DecTab& tab = tt.t;
+  int k = 0;
+  tab.cum[0] = 0;
+  for (int l = 0; l < nl; ++l) {
+    if (!((level_mask >> l) & 1)) continue;
+    tab.y[k] = ys[l];
+    tab.sb[k] = strides[3 * l];
+    tab.sh[k] = strides[3 * l + 1];
+    tab.sw[k] = strides[3 * l + 2];
+    tab.H[k] = hw[2 * l];
+    tab.W[k] = hw[2 * l + 1];
+    tab.stride[k] = lvl_stride[l];
+    tab.zoff[k] = zoff;
+    tt.lvl[k] = l;
+    zoff += (long)na * tab.H[k] * tab.W[k];
+    tab.cum[k + 1] = tab.cum[k] + (long)N * na * tab.H[k] * tab.W[k] * no;
+    ++k;
+  }
+  if (zoff > ztotal) return (int)hipErrorInvalidValue;  // the pass's rows must fit the combined buffer
+  if (k == 0) return (int)hipSuccess;
+  tab.nl = k;
+  const int g = grid_cap(ceil_div(tab.cum[k], 256), 8192);
+  hipStream_t st = (hipStream_t)stream;
+  if (dtype) decode_tta_kernel<bf16><<<g, 256, 0, st>>>(tt, N, na, no, anchors, z, ztotal, scale, flip, img_h, img_w);
+  else decode_tta_kernel<float><<<g, 256, 0, st>>>(tt, N, na, no, anchors, z, ztotal, scale, flip, img_h, img_w);
   return (int)hipGetLastError();
 }
 

@@ -95,9 +95,12 @@ SIGNATURES = {
     'dmy_nhwc_to_nchw_f32': [I, P, L, P, I, I, I, I, P],
     'dmy_pointwise': [I, I, I, P, P, P, L, F, P],
     'dmy_cast': [I, I, P, P, L, F, P],
+    # tta.hip
+    'dmy_tta_image': [I, I, P, P, I, I, I, I, I, I, F, I, I, I, I, I, F, P],
     # detect_loss.hip
     'dmy_detect_decode': [I, P, L, L, L, I, I, I, I, I, F, P, P, L, L, P],
     'dmy_detect_decode_levels': [I, I, P, P, P, P, I, I, I, P, P, L, P],
+    'dmy_detect_decode_tta': [I, I, P, P, P, P, I, I, I, P, P, L, F, I, F, F, I, L, P],
     'dmy_build_targets': [P, I, P, I, I, I, F, P, P, P, P, P, P, P, P, P],
     'dmy_yolo_loss_part_rows': [],
     'dmy_yolo_loss_level': [I, P, L, L, L, L, I, I, I, I, I, I, F, F, F, F, F, F, F, F, F, P, P, P, P, P, P, P, P,

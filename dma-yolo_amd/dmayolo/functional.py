@@ -1232,6 +1232,40 @@ def image_s2d(x, dtype):
     return buf
 
 
+def tta_image(x, dtype, ratio, flip, gs, s2d):
+    """One test-time-augmentation input (models/yolo.py:201: scale_img(x.flip(flip) if flip else x, ratio, gs=gs),
+    utils/torch_utils.py:264-274) as the stem's input, in one launch (csrc dmy_tta_image): NCHW uint8 (/255) or float
+    image -> flip (None / 0, 2 up-down, 3 left-right) -> bilinear resize to (int(H*ratio), int(W*ratio)) -> 0.447 pad to
+    the next gs multiple -> `dtype` in NHWC storage, space-to-depth (`_dmy_s2d`, as image_s2d) or channel-padded
+    (`_dmy_cpad`, as Model.to_input's ToNHWC).  No gradient."""
+    import math
+    N, C, H, W = x.shape
+    flip = int(flip or 0)
+    if ratio == 1.0:
+        OH, OW, OHp, OWp = H, W, H, W
+    else:
+        OH, OW = int(H * ratio), int(W * ratio)
+        OHp, OWp = (math.ceil(v * ratio / gs) * gs for v in (H, W))
+    xc = x.detach().contiguous()
+    kind, scale = (0, 1.0 / 255.0) if x.dtype == torch.uint8 else (1, 1.0)
+    if kind and xc.dtype != torch.float32:
+        xc = xc.float()
+    if s2d:
+        Cs = -(-4 * C // VW[dtype]) * VW[dtype]
+        buf = torch.empty((N, Cs, OHp // 2, OWp // 2), dtype=dtype, device=x.device, memory_format=CL)
+    else:
+        Cs = -(-C // VW[dtype]) * VW[dtype]
+        buf = torch.empty((N, Cs, OHp, OWp), dtype=dtype, device=x.device, memory_format=CL)
+    call('dmy_tta_image', DT[dtype], kind, ptr(xc), ptr(buf), N, C, H, W, int(bool(s2d)), Cs, scale, flip, OH, OW, OHp,
+         OWp, 0.447, stream())
+    if s2d:
+        buf._dmy_s2d = C
+        return buf
+    y = buf[:, :C] if Cs != C else buf
+    y._dmy_cpad = Cs
+    return y
+
+
 class ToNHWC(torch.autograd.Function):
     """NCHW float/uint8 image -> NHWC storage dtype (train.py:402 `/255` when uint8).  The pixel
     stride is rounded up to a 16-byte vector with zero channels so the stem conv stays vectorised."""

@@ -44,10 +44,17 @@ class GraphedDetector:
             self.static_out = self.model(self.static_in)
         self.key = self._state_key(x)
 
-    def _capture_detect(self, x, nms_args):
+    def _capture_detect(self, x, nms_args, augment=False):
         from .utils.general import nms_prepare, nms_launch, nms_buffers
         self._capture(x)  # warm-up forwards fill every per-layer cache; the forward-only graph stays usable
         z = self.static_out[0]
+        if augment:  # the augmented passes run at other input sizes: fill their caches too, outside the capture
+            ws = torch.cuda.Stream()
+            ws.wait_stream(torch.cuda.current_stream())
+            with torch.cuda.stream(ws), torch.no_grad():
+                for _ in range(self.warmup):
+                    z = self.model(self.static_in, augment=True)[0]
+            torch.cuda.current_stream().wait_stream(ws)
         pred, plan = nms_prepare(z, **nms_args)  # NMS plan from the recorded output's shape (the cap hint)
         # the detect graph owns its input buffer, its state key and its NMS counter / pinned counts: __call__ may
         # re-record the forward-only graph (and replace static_in) without this graph noticing otherwise
@@ -61,18 +68,23 @@ class GraphedDetector:
         torch.cuda.synchronize()
         self.dgraph = torch.cuda.CUDAGraph()
         with torch.cuda.graph(self.dgraph, stream=cs), torch.no_grad():
-            out = self.model(self.dstatic_in)
+            # augment: five dmy_tta_image launches, six forwards and six dmy_detect_decode_tta launches, in sequence
+            # on the capture stream (no parallel branches)
+            out = self.model(self.dstatic_in, augment=True) if augment else self.model(self.dstatic_in)
             dpred = out[0].detach().float().contiguous()  # nms_prepare's conversion (the plan, cls_ok included, is made)
             self.dstate = (out, plan, plan['cap']) + nms_launch(dpred, plan, bufs=bufs)
         self.dbufs = bufs
-        self.dkey = (self._state_key(x), tuple(sorted((k, str(v)) for k, v in nms_args.items())), plan['cap'])
+        self.dkey = (self._state_key(x), tuple(sorted((k, str(v)) for k, v in nms_args.items())), plan['cap'],
+                     bool(augment))
 
     @torch.no_grad()
     def detect(self, x, conf_thres=0.25, iou_thres=0.45, classes=None, agnostic=False, multi_label=False,
-               max_det=300):
+               max_det=300, augment=False):
         """eval forward + non_max_suppression (utils/general.py:633-725 arguments, merge=False) as one graph replay:
         returns (list of (k, 6) detections per image, (z, per-level outputs)).  The detections are views of the
-        graph's static output buffer, valid until the next call (as the forward's outputs are)."""
+        graph's static output buffer, valid until the next call (as the forward's outputs are).  augment: the
+        test-time-augmented forward (detect.py --augment) in the same single graph; the second output is then
+        (z, None)."""
         from .utils.general import nms_finish, non_max_suppression, _CAP_HINT
         if self.model.training:
             self.model.eval()
@@ -80,15 +92,15 @@ class GraphedDetector:
                     multi_label=multi_label, max_det=max_det)
         key = tuple(sorted((k, str(v)) for k, v in args.items()))
         cur = getattr(self, 'dkey', None)
-        if (cur is None or self._state_key(x) != cur[0] or cur[1] != key or
+        if (cur is None or self._state_key(x) != cur[0] or cur[1] != key or cur[3] != bool(augment) or
                 _CAP_HINT.get(self.dstate[1]['key'], cur[2]) != cur[2]):
-            self._capture_detect(x, args)
+            self._capture_detect(x, args, augment)
         self.dstatic_in.copy_(x)
         self.dgraph.replay()
         out, plan, cap, cnt, dets = self.dstate
         res = nms_finish(plan, cap, cnt, dets)
         if res is None:  # more candidates than the recorded capacity: this call eager at the exact one, next re-records
-            res = non_max_suppression(out[0], **args)
+            res = non_max_suppression(self.model(x, augment=True)[0] if augment else out[0], **args)
         return res, out
 
     @torch.no_grad()

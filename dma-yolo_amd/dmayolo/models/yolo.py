@@ -48,6 +48,13 @@ class Detect(nn.Module):
 
     def forward(self, x, sinks=None):
         """sinks: None or one GradSink-or-None per level input (Model fan-out), one contribution each"""
+        out = self.maps(x, sinks)
+        if self.training:
+            return out
+        return self.decode(out), out
+
+    def maps(self, x, sinks=None):
+        """the per-level head outputs [bs, na, ny, nx, no] (views), before any decode"""
         out = []
         for i in range(self.nl):
             sk = sinks[i].expect(1) if sinks is not None and sinks[i] is not None else None
@@ -55,9 +62,7 @@ class Detect(nn.Module):
             bs, _, ny, nx = y.shape
             # NHWC [bs, ny, nx, na*no] -> [bs, na, ny, nx, no] view (no copy)
             out.append(y.permute(0, 2, 3, 1).view(bs, ny, nx, self.na, self.no).permute(0, 3, 1, 2, 4))
-        if self.training:
-            return out
-        return self.decode(out), out
+        return out
 
     @torch.no_grad()
     def decode(self, out):
@@ -125,6 +130,45 @@ def _out_hw(m, hw):
     return hw
 
 
+TTA_SCALES = (1, 1, 0.83, 0.83, 0.67, 0.67)  # models/yolo.py:196
+TTA_FLIPS = (0, 3, 0, 3, 0, 3)  # models/yolo.py:197 (None -> 0; 2 up-down, 3 left-right)
+
+
+def tta_plan(h, w, gs, level_hw_fn, na=3):
+    """Host plan of the augmented forward (models/yolo.py:194-209, 266-275; utils/torch_utils.py:264-274) for an
+    h x w image: ([(ratio, flip, (OH, OW), (OHp, OWp), level_mask, zoff) per pass], total_rows).  The image is resized
+    to OH x OW and padded to OHp x OWp (scale_img's own float arithmetic); `level_hw_fn(OHp, OWp)` gives the Detect
+    levels' (ny, nx) at that size, `na` anchors each.  `level_mask` has a bit per level the pass keeps: _clip_augmented
+    drops the last level's rows of the first pass and the first level's rows of the last pass; `zoff` is the pass's
+    first row in the concatenated result."""
+    if h % gs or w % gs:
+        # the clip indices are whole levels only then (and the reference's own Concat layers need it)
+        raise ValueError(f'augment=True needs an image size that is a multiple of the max stride {gs}, got {h}x{w}')
+    sizes, rows = [], []
+    for ratio in TTA_SCALES:
+        if ratio == 1.0:
+            oh, ow, ohp, owp = h, w, h, w
+        else:
+            oh, ow = int(h * ratio), int(w * ratio)
+            ohp, owp = (math.ceil(v * ratio / gs) * gs for v in (h, w))
+        sizes.append(((oh, ow), (ohp, owp)))
+        rows.append([na * ny * nx for ny, nx in level_hw_fn(ohp, owp)])
+    nl = len(rows[0])
+    g = sum(4 ** x for x in range(nl))
+    full = (1 << nl) - 1
+    masks = [full] * len(TTA_SCALES)
+    # _clip_augmented with e = 1: the index formulas must land on one whole level
+    if (sum(rows[0]) // g) * 1 != rows[0][-1] or (sum(rows[-1]) // g) * 4 ** (nl - 1) != rows[-1][0]:
+        raise ValueError(f'augment=True: the clipped tails are not whole Detect levels at {h}x{w}')
+    masks[0] &= ~(1 << (nl - 1))
+    masks[-1] &= ~1
+    passes, zoff = [], 0
+    for ratio, flip, (s, sp), r, mask in zip(TTA_SCALES, TTA_FLIPS, sizes, rows, masks):
+        passes.append((ratio, flip, s, sp, mask, zoff))
+        zoff += sum(v for l, v in enumerate(r) if (mask >> l) & 1)
+    return passes, zoff
+
+
 class Model(nn.Module):
     """models/yolo.py:117-350."""
 
@@ -166,7 +210,8 @@ class Model(nn.Module):
         initialize_weights(self)
 
     def _probe_hw(self, s):
-        ys, hw = [], (s, s)
+        """the Detect inputs' (H, W) for an s x s image (or an (h, w) pair), from the layers' shapes alone"""
+        ys, hw = [], (tuple(s) if isinstance(s, (tuple, list)) else (s, s))
         for m in self.model:
             if m.f != -1:
                 hw = ys[m.f] if isinstance(m.f, int) else [hw if j == -1 else ys[j] for j in m.f]
@@ -180,10 +225,74 @@ class Model(nn.Module):
 
     def forward(self, x, augment=False, profile=False, visualize=False):
         if augment:
-            raise NotImplementedError('test-time augmentation is outside the DMA-YOLO hot path')
+            if torch.jit.is_tracing():
+                raise NotImplementedError('augment=True cannot be traced (the traced forward is one plain-path op)')
+            return self._forward_augment(x)
         if torch.jit.is_tracing():
             return _traced_forward(self, x)
         return self._forward_once(x)
+
+    # ---- test-time augmentation (models/yolo.py:194-275): six passes, each input prepared by one dmy_tta_image
+    # launch and each Detect output decoded, de-scaled, de-flipped and clipped by one dmy_detect_decode_tta launch
+    # straight into its rows of the combined tensor
+    def _tta_plan(self, h, w):
+        det = self.model[-1]
+        key = (h, w)
+        c = getattr(self, '_tta_plans', None)
+        if c is None:
+            c = self._tta_plans = {}
+        if key not in c:
+            c[key] = tta_plan(h, w, int(max(self._stride_list())), lambda hp, wp: self._probe_hw((hp, wp)), det.na)
+        return c[key]
+
+    def _stride_list(self):
+        det = self.model[-1]
+        sl = getattr(det, 'stride_list', None)
+        if not sl or len(sl) != det.nl:  # host copy: no device read per forward (graph-capturable)
+            sl = det.stride_list = [float(v) for v in det.stride.cpu()]
+        return sl
+
+    def _tta_passes(self, x):
+        """yields (plan entry, prepared input) per pass; pass 0 is the plain input, the others one launch each"""
+        if x.dim() != 4 or not x.is_cuda or getattr(x, '_dmy_s2d', 0):
+            raise ValueError('augment=True takes an NCHW image batch on the GPU')
+        passes, _ = self._tta_plan(int(x.shape[2]), int(x.shape[3]))
+        gs = int(max(self._stride_list()))
+        s2d = bool(self._s2d_stem(x))
+        for k, p in enumerate(passes):
+            yield p, (self.to_input(x) if k == 0 else Fn.tta_image(x, self.act_dtype, p[0], p[1], gs, s2d))
+
+    def tta_inputs(self, x):
+        """the six inputs of the augmented forward (scale_img(x.flip(f) if f else x, s, gs) per pass), each prepared
+        as `to_input` prepares the plain one"""
+        return [xi for _, xi in self._tta_passes(x)]
+
+    @torch.no_grad()
+    def _forward_augment(self, x):
+        det = self.model[-1]
+        if isinstance(det, TDetect):
+            raise NotImplementedError('augment=True is defined for the anchor-based Detect head only '
+                                      '(_descale_pred does not fit the TDetect output)')
+        if self.training:
+            raise RuntimeError('augment=True is an eval-mode forward: call model.eval() first')
+        bs, _, h, w = x.shape
+        passes, total = self._tta_plan(int(h), int(w))
+        z = torch.empty((bs, total, det.no), dtype=torch.float32, device=x.device)
+        anchors = det.anchors.float().contiguous()
+        sl = self._stride_list()
+        nl = det.nl
+        ls = (ctypes.c_float * nl)(*sl)
+        for (ratio, flip, _, (hp, wp), mask, zoff), xi in self._tta_passes(x):
+            out = self._forward_once(xi, raw=True)
+            lhw = [(p.shape[2], p.shape[3]) for p in out]
+            if lhw != [tuple(v) for v in self._probe_hw((hp, wp))] or len({p.dtype for p in out}) != 1:
+                raise RuntimeError(f'augment=True: head maps {lhw} do not match the plan for a {hp}x{wp} pass')
+            ys = (ctypes.c_void_p * nl)(*[p.data_ptr() for p in out])
+            st = (ctypes.c_long * (3 * nl))(*[v for p in out for v in (p.stride(0), p.stride(2), p.stride(3))])
+            hw = (ctypes.c_int * (2 * nl))(*[v for p in out for v in (p.shape[2], p.shape[3])])
+            call('dmy_detect_decode_tta', dcode(out[0]), nl, ys, st, hw, ls, bs, det.na, det.no, ptr(anchors), ptr(z),
+                 total, float(ratio), int(flip), float(h), float(w), mask, zoff, stream())
+        return z, None
 
     def _s2d_stem(self, x):
         """layer 0 is the k6 s2 p2 stem Conv (every yolov5* / DMA-YOLO yaml) and the image allows the
@@ -227,7 +336,8 @@ class Model(nn.Module):
             lay = self._arena_layout = ((first.data_ptr(), first.device), offs, n)
         return Fn.WgradArena(torch.zeros(lay[2], dtype=torch.float32, device=first.device), lay[1])
 
-    def _forward_once(self, x, profile=False, visualize=False):
+    def _forward_once(self, x, profile=False, visualize=False, raw=False):
+        """raw: stop before the Detect decode and return the head maps (the augmented forward decodes them itself)"""
         x = self.to_input(x)
         if self._cat_plans is None:
             self._cat_plans = {}
@@ -254,7 +364,10 @@ class Model(nn.Module):
                     if c not in bufs:
                         bufs[c] = Fn.concat_buffer(*shp, x if torch.is_tensor(x) else x[0])
                     kw = dict(kw or {}, out=bufs[c][:, c0:c0 + C])
-                x = m(x, **kw) if kw else m(x)
+                if raw and m is self.model[-1]:
+                    x = m.maps(x)
+                else:
+                    x = m(x, **kw) if kw else m(x)
                 y.append(x if m.i in self.save else None)
                 if shapes is not None:
                     shapes.append(tuple(x.shape) if torch.is_tensor(x) else None)

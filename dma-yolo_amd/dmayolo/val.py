@@ -75,8 +75,12 @@ def summarize(stats, nc):
 
 
 @torch.no_grad()
-def run(model, batches, nc, conf_thres=0.001, iou_thres=0.6, max_det=300, single_cls=False, compute_loss=None):
-    """Returns ((mp, mr, map50, map, *loss), maps [nc], seen, nt [nc]) like val.py:303-311."""
+def run(model, batches, nc, conf_thres=0.001, iou_thres=0.6, max_det=300, single_cls=False, compute_loss=None,
+        augment=False):
+    """Returns ((mp, mr, map50, map, *loss), maps [nc], seen, nt [nc]) like val.py:303-311.  augment: the model's
+    test-time-augmented forward (val.py:213); it has no per-level outputs, so it excludes compute_loss."""
+    if augment and compute_loss:
+        raise ValueError('augment=True returns no per-level outputs for compute_loss (val.py:213-217)')
     device = next(model.parameters()).device
     was_training = model.training
     model.eval()
@@ -90,7 +94,7 @@ def run(model, batches, nc, conf_thres=0.001, iou_thres=0.6, max_det=300, single
         img = img.to(device, non_blocking=True)
         targets = targets.to(device).float()
         nb, _, height, width = img.shape
-        out, train_out = model(img)
+        out, train_out = model(img, augment=True) if augment else model(img)
         if compute_loss:
             loss += compute_loss([x.float() for x in train_out], targets)[1]
         targets[:, 2:] *= torch.tensor([width, height, width, height], device=device, dtype=torch.float32)

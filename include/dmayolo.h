@@ -207,6 +207,13 @@ int dmy_image_s2d(int dtype, int src_kind, const void* x, void* y, int N, int C,
                   void* stream);
 int dmy_nchw_to_nhwc(int dtype, int src_kind, const void* x, void* y, int N, int C, int H, int W, int Cp, float scale,
                      void* stream);
+/* one test-time-augmentation input (models/yolo.py:199-201 with utils/torch_utils.py:264-274 scale_img): the NCHW
+ * image (src_kind / scale as dmy_image_s2d) flipped (0 none, 2 up-down, 3 left-right), resized to OH x OW
+ * (F.interpolate bilinear, align_corners=False), padded right / bottom with pad_value to OHp x OWp, in the stem's
+ * layout: s2d = 1 [N][OHp/2][OWp/2][Cs] as dmy_image_s2d (OHp, OWp even), s2d = 0 [N][OHp][OWp][Cs] as
+ * dmy_nchw_to_nhwc; channels past the image's are zero */
+int dmy_tta_image(int dtype, int src_kind, const void* x, void* y, int N, int C, int H, int W, int s2d, int Cs,
+                  float scale, int flip, int OH, int OW, int OHp, int OWp, float pad_value, void* stream);
 int dmy_nhwc_to_nchw_f32(int dtype, const void* x, long xps, float* y, int N, int C, int H, int W, void* stream);
 int dmy_pointwise(int dtype, int op, int act, const void* a, const void* b, void* y, long n, float alpha,
                   void* stream);
@@ -222,6 +229,14 @@ int dmy_detect_decode(int dtype, const void* y, long sb, long sh, long sw, int N
 int dmy_detect_decode_levels(int dtype, int nl, const void* const* ys, const long* strides, const int* hw,
                              const float* lvl_stride, int N, int na, int no, const float* anchors, float* z, long ztotal,
                              void* stream);
+/* one test-time-augmentation pass written into its slice of the combined [N][ztotal][no] buffer
+   (models/yolo.py:194-275: _forward_augment, _descale_pred, _clip_augmented): dmy_detect_decode_levels' arguments and
+   arithmetic, then xywh / scale (IEEE division) and x = img_w - x (flip 3) or y = img_h - y (flip 2).  Levels whose
+   level_mask bit is clear are neither read nor written; a kept level's rows start at zoff plus the kept earlier
+   levels' na*H*W */
+int dmy_detect_decode_tta(int dtype, int nl, const void* const* ys, const long* strides, const int* hw,
+                          const float* lvl_stride, int N, int na, int no, const float* anchors, float* z, long ztotal,
+                          float scale, int flip, float img_h, float img_w, int level_mask, long zoff, void* stream);
 int dmy_build_targets(const float* targets, int nt, const float* anchors, int na, int H, int W, float anchor_t,
                       int* b, int* a, int* gj, int* gi, int* tcls, float* tbox, float* anch, int* count,
                       void* stream);
