@@ -11,6 +11,9 @@
 //    integer atomicMax on non-negative float bits -> deterministic.  Per-target gradients are summed per cell in
 //    ascending target order (the reference's index_put_ accumulate order) and the loss sums go through per-block
 //    partials reduced in a fixed order: no float atomics, the loss and dL/dp are run-to-run bit-identical.
+//  * focal loss + autobalance: utils/loss.py:35-62 (FocalLoss around BCEcls / BCEobj, alpha 0.25, mean) and
+//    utils/loss.py:207-212 (per-level objectness balance, updated by the finalize kernel on the device).  These are
+//    the EX = true instances of the level kernels; the EX = false instances are the plain-BCE path, unchanged.
 // Everything stays on device: target counts are read by the kernels, never by the host.
 #include "common.h"
 #include "dual.h"
@@ -262,6 +265,47 @@ DEV float bce(float x, float t, float pw, float* g) {
   return l;
 }
 
+// focal form of the element, utils/loss.py:45-55: with l = bce(x, t, pw), s = sigmoid(x),
+//   pt = t s + (1 - t)(1 - s),  af = t alpha + (1 - t)(1 - alpha),  m = (1 - pt)^gamma,  L = l af m,
+//   dL/dx = af (m dl/dx - l gamma (1 - pt)^(gamma - 1) (2t - 1) s (1 - s)).
+// gmode picks the power: 1 / 2 / 3 are gamma = 1 / 1.5 / 2 by multiplies and sqrtf, 4 is full-precision powf for any
+// other gamma of the evolve range (0, 2]; 0 is gamma = 0, the plain BCE element.
+// Saturation rule: where 1 - pt == 0 (the fp32 sigmoid has saturated onto the target) the second term is taken as 0.
+// For gamma >= 1 that is what torch's autograd gives ((1 - pt)^(gamma - 1) is finite and s (1 - s) is 0 there); for
+// gamma < 1 torch multiplies inf by 0 and returns NaN, here the gradient stays finite.  1 - pt is clamped at 0, so
+// a last-bit overshoot of pt cannot reach sqrtf / powf as a negative base.
+constexpr float kFocalAlpha = 0.25f;
+DEV float focal_bce(float x, float t, float pw, float gamma, int gmode, float* g) {
+  float dl;
+  const float l = bce(x, t, pw, &dl);
+  if (gmode == 0) {
+    *g = dl;
+    return l;
+  }
+  const float s = 1.f / (1.f + expf(-x));
+  const float pt = t * s + (1.f - t) * (1.f - s);
+  const float af = t * kFocalAlpha + (1.f - t) * (1.f - kFocalAlpha);
+  const float u = fmaxf(1.f - pt, 0.f);
+  float m, dm;  // u^gamma, gamma u^(gamma - 1)
+  switch (gmode) {
+    case 1: m = u; dm = 1.f; break;
+    case 2: { const float r = sqrtf(u); m = u * r; dm = 1.5f * r; break; }
+    case 3: m = u * u; dm = 2.f * u; break;
+    default: m = powf(u, gamma); dm = gamma * powf(u, gamma - 1.f); break;
+  }
+  if (u == 0.f) dm = 0.f;
+  *g = af * (m * dl - l * dm * (2.f * t - 1.f) * (s * (1.f - s)));
+  return l * (af * m);
+}
+
+// what the EX = true level kernels take on top of LossCfg: the ComputeLoss object's per-level balance (device state,
+// read instead of cfg.balance), this level's index, the focal gamma and its power mode
+struct LossEx {
+  const double* balance;
+  int level, gmode;
+  float gamma;
+};
+
 struct LossCfg {
   float box_gain, obj_gain, cls_gain, cls_pw, obj_pw, cp, cn, balance, bs;
   int nc, na, no, N, H, W;
@@ -276,8 +320,8 @@ constexpr int LOSS_PMAX = 2048;
 // cell's box / cls channels goes to tgrad[j][4 + nc] (no atomics), and j is pushed on its cell's list (head / nxt);
 // loss_combine_kernel then sums each cell's contributions in ascending j -- the order of the reference's
 // index_put_(accumulate=True) backward of pi[b, a, gj, gi] (utils/loss.py:179).
-template <typename T>
-__global__ void loss_targets_kernel(const T* __restrict__ p, LossCfg cfg, const int* __restrict__ tb,
+template <typename T, bool EX>
+__global__ void loss_targets_kernel(const T* __restrict__ p, LossCfg cfg, LossEx ex, const int* __restrict__ tb,
                                     const int* __restrict__ ta, const int* __restrict__ tgj, const int* __restrict__ tgi,
                                     const int* __restrict__ tcls, const float* __restrict__ tbox,
                                     const float* __restrict__ anch, const int* __restrict__ count,
@@ -315,7 +359,10 @@ __global__ void loss_targets_kernel(const T* __restrict__ p, LossCfg cfg, const 
       const int tc = tcls[j];
       for (int c = 0; c < cfg.nc; ++c) {
         float d;
-        lcls += bce(to_f(ps[5 + c]), c == tc ? cfg.cp : cfg.cn, cfg.cls_pw, &d);
+        if constexpr (EX)
+          lcls += focal_bce(to_f(ps[5 + c]), c == tc ? cfg.cp : cfg.cn, cfg.cls_pw, ex.gamma, ex.gmode, &d);
+        else
+          lcls += bce(to_f(ps[5 + c]), c == tc ? cfg.cp : cfg.cn, cfg.cls_pw, &d);
         g[4 + c] = cg * d;
       }
     }
@@ -385,12 +432,16 @@ __global__ void loss_combine_kernel(LossCfg cfg, const int* __restrict__ tb, con
   }
 }
 
-// dense objectness BCE over every (b, a, h, w); writes the obj-channel gradient
-template <typename T>
-__global__ void loss_obj_kernel(const T* __restrict__ p, LossCfg cfg, const float* __restrict__ tobj,
+// dense objectness BCE over every (b, a, h, w); writes the obj-channel gradient.  EX: the focal element, the balance
+// read from device state, and the level's partial left unbalanced (the finalize applies the balance and needs the
+// plain mean for the autobalance update)
+template <typename T, bool EX>
+__global__ void loss_obj_kernel(const T* __restrict__ p, LossCfg cfg, LossEx ex, const float* __restrict__ tobj,
                                 float* __restrict__ G, float* __restrict__ part) {
   const long total = (long)cfg.N * cfg.na * cfg.H * cfg.W;
-  const float gs = cfg.balance * cfg.obj_gain * cfg.bs / (float)total;
+  float balance = cfg.balance;
+  if constexpr (EX) balance = (float)ex.balance[ex.level];
+  const float gs = balance * cfg.obj_gain * cfg.bs / (float)total;
   float s = 0.f;
   for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
     const int w = (int)(i % cfg.W);
@@ -401,7 +452,8 @@ __global__ void loss_obj_kernel(const T* __restrict__ p, LossCfg cfg, const floa
     const int b = (int)(t / cfg.na);
     const long off = b * cfg.sb + h * cfg.sh + w * cfg.sw + (long)a * cfg.sa + 4;
     float d;
-    s += bce(to_f(p[off]), tobj[i], cfg.obj_pw, &d);
+    if constexpr (EX) s += focal_bce(to_f(p[off]), tobj[i], cfg.obj_pw, ex.gamma, ex.gmode, &d);
+    else s += bce(to_f(p[off]), tobj[i], cfg.obj_pw, &d);
     G[off] = gs * d;
   }
   __shared__ float r[16];
@@ -411,7 +463,8 @@ __global__ void loss_obj_kernel(const T* __restrict__ p, LossCfg cfg, const floa
   if (threadIdx.x == 0) {
     float q = 0.f;
     for (int k = 0; k < (int)(blockDim.x >> 6); ++k) q += r[k];
-    part[LOSS_PMAX + blockIdx.x] = q * cfg.balance / (float)total;
+    if constexpr (EX) part[LOSS_PMAX + blockIdx.x] = q / (float)total;
+    else part[LOSS_PMAX + blockIdx.x] = q * cfg.balance / (float)total;
   }
 }
 
@@ -445,6 +498,57 @@ __global__ void __launch_bounds__(256) loss_finalize_kernel(const float* __restr
     items[1] = lo;
     items[2] = lc;
     loss[0] = (lb + lo + lc) * bs;
+  }
+}
+
+// The finalize of the EX level kernels.  Row 1 of a level's partials is its plain objectness mean obji, so
+//   lobj = sum_i obji * balance[i]   with the balance from before this call (utils/loss.py:207), and then, when
+// autobalance is set, utils/loss.py:208-212 in double like the reference's Python floats:
+//   balance[i] = balance[i] * 0.9999 + 0.0001 / obji  for every level, then all divided by balance[ssi].
+// A level whose obji is 0 or not finite keeps its balance (the reference raises ZeroDivisionError on 0).  The level
+// kernels of this call have read balance[] before this kernel runs (same stream); nothing is read by the host.
+constexpr int kBalLevels = 8;
+__global__ void __launch_bounds__(256) loss_finalize_balance_kernel(const float* __restrict__ part, int nl, float box,
+                                                                    float obj, float cls, float bs,
+                                                                    double* __restrict__ balance, int autobalance,
+                                                                    int ssi, float* __restrict__ loss,
+                                                                    float* __restrict__ items) {
+  __shared__ float red[256];
+  __shared__ float rows[kBalLevels][3];
+  for (int lvl = 0; lvl < nl; ++lvl)
+    for (int r = 0; r < 3; ++r) {
+      const float* pr = part + ((long)lvl * 3 + r) * LOSS_PMAX;
+      float v = 0.f;
+      for (int k = threadIdx.x; k < LOSS_PMAX; k += 256) v += pr[k];
+      red[threadIdx.x] = v;
+      __syncthreads();
+      for (int h = 128; h > 0; h >>= 1) {
+        if ((int)threadIdx.x < h) red[threadIdx.x] += red[threadIdx.x + h];
+        __syncthreads();
+      }
+      if (threadIdx.x == 0) rows[lvl][r] = red[0];
+      __syncthreads();
+    }
+  if (threadIdx.x == 0) {
+    float tb = 0.f, to = 0.f, tc = 0.f;
+    for (int lvl = 0; lvl < nl; ++lvl) {
+      tb += rows[lvl][0];
+      to += rows[lvl][1] * (float)balance[lvl];
+      tc += rows[lvl][2];
+    }
+    const float lb = tb * box, lo = to * obj, lc = tc * cls;
+    items[0] = lb;
+    items[1] = lo;
+    items[2] = lc;
+    loss[0] = (lb + lo + lc) * bs;
+    if (autobalance) {
+      for (int lvl = 0; lvl < nl; ++lvl) {
+        const double o = (double)rows[lvl][1];
+        if (o != 0.0 && isfinite(o)) balance[lvl] = balance[lvl] * 0.9999 + 0.0001 / o;
+      }
+      const double d = balance[ssi];
+      for (int lvl = 0; lvl < nl; ++lvl) balance[lvl] = balance[lvl] / d;
+    }
   }
 }
 
@@ -557,21 +661,64 @@ DMY_API int dmy_yolo_loss_level(int dtype, const void* p, long sb, long sa, long
   int* head = links;
   int* nxt = links + cells;
   (void)hipMemsetAsync(head, 0xff, sizeof(int) * (size_t)cells, st);  // empty lists (-1)
+  const LossEx ex{};
   if (dtype)
-    loss_targets_kernel<bf16><<<gt, 256, 0, st>>>((const bf16*)p, cfg, tb, ta, tgj, tgi, tcls, tbox, anch, count,
-                                                  tgrad, head, nxt, tobj, part);
+    loss_targets_kernel<bf16, false><<<gt, 256, 0, st>>>((const bf16*)p, cfg, ex, tb, ta, tgj, tgi, tcls, tbox, anch,
+                                                         count, tgrad, head, nxt, tobj, part);
   else
-    loss_targets_kernel<float><<<gt, 256, 0, st>>>((const float*)p, cfg, tb, ta, tgj, tgi, tcls, tbox, anch, count,
-                                                   tgrad, head, nxt, tobj, part);
+    loss_targets_kernel<float, false><<<gt, 256, 0, st>>>((const float*)p, cfg, ex, tb, ta, tgj, tgi, tcls, tbox, anch,
+                                                          count, tgrad, head, nxt, tobj, part);
   loss_combine_kernel<<<gt, 256, 0, st>>>(cfg, tb, ta, tgj, tgi, count, tgrad, head, nxt, G);
-  if (dtype) loss_obj_kernel<bf16><<<go, 256, 0, st>>>((const bf16*)p, cfg, tobj, G, part);
-  else loss_obj_kernel<float><<<go, 256, 0, st>>>((const float*)p, cfg, tobj, G, part);
+  if (dtype) loss_obj_kernel<bf16, false><<<go, 256, 0, st>>>((const bf16*)p, cfg, ex, tobj, G, part);
+  else loss_obj_kernel<float, false><<<go, 256, 0, st>>>((const float*)p, cfg, ex, tobj, G, part);
+  return (int)hipGetLastError();
+}
+
+// dmy_yolo_loss_level with the focal element (fl_gamma > 0; 0 = plain BCE) and the balance read from balance[level]
+// on the device.  Same buffers and workspaces; the level's objectness partials are left unbalanced, so they go to
+// dmy_yolo_loss_finalize_balance, not dmy_yolo_loss_finalize.
+DMY_API int dmy_yolo_loss_level_focal(int dtype, const void* p, long sb, long sa, long sh, long sw, int N, int na, int H,
+                                      int W, int no, int nc, float box_gain, float obj_gain, float cls_gain,
+                                      float cls_pw, float obj_pw, float cp, float cn, const double* balance, int level,
+                                      float fl_gamma, float bs, const int* tb, const int* ta, const int* tgj,
+                                      const int* tgi, const int* tcls, const float* tbox, const float* anch,
+                                      const int* count, int cap, float* G, float* tobj, float* part, float* tgrad,
+                                      int* links, void* stream) {
+  if (!(fl_gamma >= 0.f) || level < 0 || level >= kBalLevels || balance == nullptr) return (int)hipErrorInvalidValue;
+  hipStream_t st = (hipStream_t)stream;
+  LossCfg cfg{box_gain, obj_gain, cls_gain, cls_pw, obj_pw, cp, cn, 0.f, bs, nc, na, no, N, H, W, sb, sa, sh, sw};
+  const int gmode = fl_gamma == 0.f ? 0 : fl_gamma == 1.f ? 1 : fl_gamma == 1.5f ? 2 : fl_gamma == 2.f ? 3 : 4;
+  const LossEx ex{balance, level, gmode, fl_gamma};
+  const int gt = grid_cap(ceil_div(cap, 256), 1024);
+  const long cells = (long)N * na * H * W;
+  const int go = grid_cap(ceil_div(cells, 256), LOSS_PMAX);
+  int* head = links;
+  int* nxt = links + cells;
+  (void)hipMemsetAsync(head, 0xff, sizeof(int) * (size_t)cells, st);  // empty lists (-1)
+  if (dtype)
+    loss_targets_kernel<bf16, true><<<gt, 256, 0, st>>>((const bf16*)p, cfg, ex, tb, ta, tgj, tgi, tcls, tbox, anch,
+                                                        count, tgrad, head, nxt, tobj, part);
+  else
+    loss_targets_kernel<float, true><<<gt, 256, 0, st>>>((const float*)p, cfg, ex, tb, ta, tgj, tgi, tcls, tbox, anch,
+                                                         count, tgrad, head, nxt, tobj, part);
+  loss_combine_kernel<<<gt, 256, 0, st>>>(cfg, tb, ta, tgj, tgi, count, tgrad, head, nxt, G);
+  if (dtype) loss_obj_kernel<bf16, true><<<go, 256, 0, st>>>((const bf16*)p, cfg, ex, tobj, G, part);
+  else loss_obj_kernel<float, true><<<go, 256, 0, st>>>((const float*)p, cfg, ex, tobj, G, part);
   return (int)hipGetLastError();
 }
 
 DMY_API int dmy_yolo_loss_finalize(const float* part, int nl, float box, float obj, float cls, float bs, float* loss,
                                    float* items, void* stream) {
   loss_finalize_kernel<<<1, 256, 0, (hipStream_t)stream>>>(part, nl, box, obj, cls, bs, loss, items);
+  return (int)hipGetLastError();
+}
+
+DMY_API int dmy_yolo_loss_finalize_balance(const float* part, int nl, float box, float obj, float cls, float bs,
+                                           double* balance, int autobalance, int ssi, float* loss, float* items,
+                                           void* stream) {
+  if (nl < 1 || nl > kBalLevels || balance == nullptr || ssi < 0 || ssi >= nl) return (int)hipErrorInvalidValue;
+  loss_finalize_balance_kernel<<<1, 256, 0, (hipStream_t)stream>>>(part, nl, box, obj, cls, bs, balance, autobalance,
+                                                                   ssi, loss, items);
   return (int)hipGetLastError();
 }
 

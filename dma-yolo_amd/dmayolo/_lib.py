@@ -106,6 +106,9 @@ SIGNATURES = {
     'dmy_yolo_loss_level': [I, P, L, L, L, L, I, I, I, I, I, I, F, F, F, F, F, F, F, F, F, P, P, P, P, P, P, P, P,
                             I, P, P, P, P, P, P],
     'dmy_yolo_loss_finalize': [P, I, F, F, F, F, P, P, P],
+    'dmy_yolo_loss_level_focal': [I, P, L, L, L, L, I, I, I, I, I, I, F, F, F, F, F, F, F, P, I, F, F, P, P, P, P, P,
+                                  P, P, P, I, P, P, P, P, P, P],
+    'dmy_yolo_loss_finalize_balance': [P, I, F, F, F, F, P, I, I, P, P, P],
     'dmy_loss_grad': [I, P, P, P, L, P],
     'dmy_siou_eval': [P, P, P, P, I, P],
     # tal.hip

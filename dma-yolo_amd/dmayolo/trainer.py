@@ -30,10 +30,12 @@ def one_cycle(y1=0.0, y2=1.0, steps=100):
 
 class Trainer:
     def __init__(self, model, hyp, batch_size, epochs=300, nb=100, adam=False, linear_lr=False, world_size=1,
-                 rank=-1, net=None, compute_loss=None, ema=True, amp=True, nbs=64, start_epoch=0):
+                 rank=-1, net=None, compute_loss=None, ema=True, amp=True, nbs=64, start_epoch=0,
+                 autobalance=False):
         """batch_size: the total batch size (train.py's opt.batch_size; each of `world_size` ranks holds
         batch_size // world_size images).  nb: batches per epoch.  hyp: the scaled hyp dict (model.hyp);
-        its weight_decay is scaled here as train.py:189-192 does."""
+        its weight_decay is scaled here as train.py:189-192 does.  autobalance: passed to the ComputeLoss built here
+        (ignored when compute_loss is given)."""
         self.model = de_parallel(model)
         self.net = net if net is not None else model
         self.hyp = hyp
@@ -55,7 +57,7 @@ class Trainer:
         self.scaler = GradScaler(dev, enabled=amp and dev.type == 'cuda', world=self.world)
         if compute_loss is None:
             from .utils.loss import ComputeLoss
-            compute_loss = ComputeLoss(self.model)
+            compute_loss = ComputeLoss(self.model, autobalance=autobalance)
         self.compute_loss = compute_loss
         self.nw = max(round(hyp['warmup_epochs'] * nb), 1000)  # train.py:345
         self.last_opt_step = -1

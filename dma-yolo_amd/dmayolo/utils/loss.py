@@ -4,6 +4,13 @@ ComputeLoss(model)(p, targets) -> (loss[1], items[3]) exactly like utils/loss.py
 sort_obj_iou forced on (loss.py:191-194) and the in-place gij clamp (loss.py:265-272).  One
 autograd Function runs build_targets + per-target SIoU/BCE + dense objectness BCE in HIP kernels
 and keeps dL/dp from the forward; backward scales it by the upstream gradient on device.
+
+hyp['fl_gamma'] > 0 wraps both BCE terms in the reference's FocalLoss (utils/loss.py:35-62, 149-152) and
+autobalance=True keeps the per-level objectness balance of utils/loss.py:207-212.  Both run in the same
+kernels through the dmy_yolo_loss_level_focal / dmy_yolo_loss_finalize_balance entries; the balance is a
+float64 device tensor owned by the ComputeLoss object and updated by the finalize kernel, so a step never
+reads it back (the reference's .item() per level) and stays graph-capturable.  With fl_gamma == 0 and
+autobalance off the original entries run, unchanged.
 """
 import torch
 
@@ -45,6 +52,7 @@ class _YoloLossFn(torch.autograd.Function):
         part = torch.zeros(nl * PR, dtype=torch.float32, device=dev)  # per-block partials, fixed-order reduction
         Gs = []
         bs = p[0].shape[0]
+        bal = cl._balance_on(dev) if (cl.fl_gamma > 0 or cl.autobalance) else None
         for i, pi in enumerate(p):
             N, na, H, W, no = pi.shape
             assert pi.stride(4) == 1, 'channel dim must be contiguous'
@@ -54,16 +62,24 @@ class _YoloLossFn(torch.autograd.Function):
             tgrad = torch.empty((cap, 4 + (cl.nc if cl.nc > 1 else 0)), dtype=torch.float32, device=dev)
             links = torch.empty(N * na * H * W + cap, dtype=torch.int32, device=dev)
             s = pi.stride()
-            call('dmy_yolo_loss_level', dcode(pi), ptr(pi), s[0], s[1], s[2], s[3], N, na, H, W, no, cl.nc,
-                 float(h['box']), float(h['obj']), float(h['cls']), float(h['cls_pw']), float(h['obj_pw']),
-                 float(cl.cp), float(cl.cn), float(cl.balance[i]), float(bs), ptr(ii[0]), ptr(ii[1]), ptr(ii[2]),
-                 ptr(ii[3]), ptr(ii[4]), ptr(tbox), ptr(anch), ptr(cnt), cap, ptr(G), ptr(tobj), ptr(part[PR * i:]),
-                 ptr(tgrad), ptr(links), stream())
+            head = (dcode(pi), ptr(pi), s[0], s[1], s[2], s[3], N, na, H, W, no, cl.nc, float(h['box']),
+                    float(h['obj']), float(h['cls']), float(h['cls_pw']), float(h['obj_pw']), float(cl.cp),
+                    float(cl.cn))
+            tail = (float(bs), ptr(ii[0]), ptr(ii[1]), ptr(ii[2]), ptr(ii[3]), ptr(ii[4]), ptr(tbox), ptr(anch),
+                    ptr(cnt), cap, ptr(G), ptr(tobj), ptr(part[PR * i:]), ptr(tgrad), ptr(links), stream())
+            if bal is None:
+                call('dmy_yolo_loss_level', *head, float(cl._balance[i]), *tail)
+            else:
+                call('dmy_yolo_loss_level_focal', *head, ptr(bal), i, float(cl.fl_gamma), *tail)
             Gs.append(G)
         loss = torch.empty(1, dtype=torch.float32, device=dev)
         items = torch.empty(3, dtype=torch.float32, device=dev)
-        call('dmy_yolo_loss_finalize', ptr(part), nl, float(h['box']), float(h['obj']), float(h['cls']), float(bs),
-             ptr(loss), ptr(items), stream())
+        if bal is None:
+            call('dmy_yolo_loss_finalize', ptr(part), nl, float(h['box']), float(h['obj']), float(h['cls']),
+                 float(bs), ptr(loss), ptr(items), stream())
+        else:  # lobj with the balance as it stood before this call, then the autobalance update, all on the device
+            call('dmy_yolo_loss_finalize_balance', ptr(part), nl, float(h['box']), float(h['obj']), float(h['cls']),
+                 float(bs), ptr(bal), int(cl.autobalance), cl.ssi, ptr(loss), ptr(items), stream())
         ctx.Gs = Gs
         ctx.dtypes = [pi.dtype for pi in p]
         ctx.mark_non_differentiable(items)
@@ -82,20 +98,56 @@ class _YoloLossFn(torch.autograd.Function):
 
 
 class ComputeLoss:
-    """utils/loss.py:135-218 (SIoU, anchor-based)."""
+    """utils/loss.py:135-218 (SIoU, anchor-based), with the focal wrapper (hyp['fl_gamma'] > 0) and autobalance.
+
+    Autobalance deviates from the reference in one place: a level whose objectness loss is exactly 0 (or not
+    finite) keeps its balance for that step, where the reference's `0.0001 / obji.item()` raises
+    ZeroDivisionError.  Under DDP every rank keeps its own balance, as in the reference."""
 
     def __init__(self, model, autobalance=False):
-        assert not autobalance, 'autobalance is off in the reference training path'
         h = model.hyp
-        if h.get('fl_gamma', 0.0) > 0:
-            raise NotImplementedError('focal loss (fl_gamma > 0) is outside the DMA-YOLO hot path')
+        self.fl_gamma = float(h.get('fl_gamma', 0.0))
+        assert 0.0 <= self.fl_gamma < float('inf'), f'fl_gamma {self.fl_gamma} must be finite and >= 0'
         self.cp, self.cn = smooth_BCE(eps=h.get('label_smoothing', 0.0))
         det = de_parallel(model).model[-1]
-        self.balance = {3: [4.0, 1.0, 0.4]}.get(det.nl, [4.0, 1.0, 0.25, 0.06, 0.02])
-        self.gr, self.hyp, self.autobalance = 1.0, h, False
+        self._balance = {3: [4.0, 1.0, 0.4]}.get(det.nl, [4.0, 1.0, 0.25, 0.06, 0.02])
+        self._balance_dev = None  # float64 on the device once the focal / autobalance path runs
+        self.ssi = [float(s) for s in det.stride].index(16.0) if autobalance else 0  # stride 16 index
+        self.gr, self.hyp, self.autobalance = 1.0, h, bool(autobalance)
         for k in ('na', 'nc', 'nl'):
             setattr(self, k, getattr(det, k))
         self.anchors = det.anchors.float().contiguous()
+        if (self.fl_gamma > 0 or self.autobalance) and self.anchors.is_cuda:
+            self._balance_on(self.anchors.device)  # allocated here, so that a first call may already be captured
+
+    def _balance_on(self, dev):
+        """the balance as device state: one float64 tensor whose address never changes (graph capture records the
+        kernels that read and update it)"""
+        if self._balance_dev is None or self._balance_dev.device != dev:
+            self._balance_dev = torch.tensor(self.balance, dtype=torch.float64, device=dev)
+        return self._balance_dev
+
+    @property
+    def balance_dev(self):
+        """the float64 device tensor the kernels read and update (None while only the plain path has run);
+        reading the attribute does not synchronise"""
+        return self._balance_dev
+
+    @property
+    def balance(self):
+        """per-level objectness balance as a list of floats (utils/loss.py:161).  With autobalance this reads the
+        device state back and synchronises; a training step never does."""
+        if self.autobalance and self._balance_dev is not None:
+            return self._balance_dev.tolist()
+        return list(self._balance)
+
+    @balance.setter
+    def balance(self, v):
+        v = [float(x) for x in v]
+        assert len(v) == len(self._balance), (len(v), len(self._balance))  # the device tensor keeps its shape
+        self._balance = v
+        if self._balance_dev is not None:
+            self._balance_dev.copy_(torch.tensor(v, dtype=torch.float64))
 
     def __call__(self, p, targets):
         return _YoloLossFn.apply(self, targets, *p)

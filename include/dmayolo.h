@@ -250,6 +250,22 @@ int dmy_yolo_loss_level(int dtype, const void* p, long sb, long sa, long sh, lon
                         int cap, float* grad, float* tobj, float* part, float* tgrad, int* links, void* stream);
 int dmy_yolo_loss_finalize(const float* part, int nl, float box, float obj, float cls, float bs, float* loss,
                            float* items, void* stream);
+/* Focal loss and autobalance.  dmy_yolo_loss_level_focal is dmy_yolo_loss_level with the FocalLoss wrapper of
+ * utils/loss.py:35-62 around both BCE terms (alpha 0.25, mean; fl_gamma 0 = plain BCE; 1, 1.5 and 2 by multiplies /
+ * sqrtf, any other gamma by powf) and with the level's objectness balance read from balance[level] (device, double)
+ * instead of passed by value.  Its objectness partials are left unbalanced and belong to
+ * dmy_yolo_loss_finalize_balance, which applies balance[] as it stood before the call and then, when autobalance
+ * is set, updates it in place as utils/loss.py:207-212 does (balance[i] = balance[i] * 0.9999 + 0.0001 / obji, all
+ * divided by balance[ssi]; a level whose obji is 0 or not finite keeps its value).  nl <= 8; no host read. */
+int dmy_yolo_loss_level_focal(int dtype, const void* p, long sb, long sa, long sh, long sw, int N, int na, int H, int W,
+                              int no, int nc, float box_gain, float obj_gain, float cls_gain, float cls_pw,
+                              float obj_pw, float cp, float cn, const double* balance, int level, float fl_gamma,
+                              float bs, const int* b, const int* a, const int* gj, const int* gi, const int* tcls,
+                              const float* tbox, const float* anch, const int* count, int cap, float* grad,
+                              float* tobj, float* part, float* tgrad, int* links, void* stream);
+int dmy_yolo_loss_finalize_balance(const float* part, int nl, float box, float obj, float cls, float bs,
+                                   double* balance, int autobalance, int ssi, float* loss, float* items,
+                                   void* stream);
 int dmy_loss_grad(int dtype, const float* grad, const float* upstream, void* dp, long n, void* stream);
 /* SIoU (utils/metrics.py:192-235, bbox_iou(..., x1y1x2y2=False, SIoU=True)) of n xywh pairs through the
  * loss kernel's device function: iou [n] and d iou / d b1 [n][4] (forward-mode duals). */

@@ -292,6 +292,82 @@ def gen_loss():
         print('wrote loss', hypname)
 
 
+def _focal_model(hypname, nc, img, gamma, **over):
+    """gen_loss's model / hyp construction with fl_gamma set (and any hyp overrides)"""
+    import yaml
+    hyp = yaml.safe_load(open(os.path.join(ref_stubs.REF, 'data', 'hyps', f'hyp.{hypname}.yaml')))
+    nl = 3
+    hyp['box'] *= 3 / nl
+    hyp['cls'] *= nc / 80 * 3 / nl
+    hyp['obj'] *= (img / 640) ** 2 * 3 / nl
+    hyp['label_smoothing'] = 0.0
+    hyp['fl_gamma'] = gamma
+    hyp.update(over)
+    torch.manual_seed(10)
+    model = Y.Model(os.path.join(ref_stubs.REF, 'models', 'yolov5n.yaml'), nc=nc)
+    model.hyp = hyp
+    return model, hyp
+
+
+def gen_focal():
+    """ComputeLoss with the FocalLoss wrapper (utils/loss.py:35-62, fl_gamma > 0) and with autobalance
+    (utils/loss.py:207-212).  Same p / target construction as gen_loss; the names stay off the loss_ prefix.
+      focal_<case>.npz       one call: meta, targets, anchors, p.i, loss, items, gp.i
+      focal_autobalance*.npz four successive calls of one ComputeLoss(model, autobalance=True) with a different p
+                             per call: p.i [4, ...], loss [4, 1], items [4, 3], balance [4, 3] (after each call),
+                             gp.i of the last call"""
+    anchors = [[10, 13, 16, 30, 33, 23], [30, 61, 62, 45, 59, 119], [116, 90, 156, 198, 373, 326]]
+    bs = 2
+
+    def meta(hyp, nc, img, **kw):
+        return json.dumps(dict(hyp=hyp, nc=nc, img=img, anchors=anchors, stride=[8, 16, 32], **kw))
+
+    for name, hypname, nc, img, gamma, over in [
+            ('visdrone', 'VisDrone', 10, 256, 1.5, {}),
+            ('scratch_ls', 'scratch', 80, 128, 2.0, dict(label_smoothing=0.1, cls_pw=0.9, obj_pw=1.1)),
+            ('g05', 'VisDrone', 10, 128, 0.5, {})]:
+        model, hyp = _focal_model(hypname, nc, img, gamma, **over)
+        p = [rnd(bs, 3, img // s, img // s, nc + 5, seed=30 + i) for i, s in enumerate((8, 16, 32))]
+        targets = synth_targets(bs, 12, nc, seed=31)
+        cl = L.ComputeLoss(model)
+        assert isinstance(cl.BCEobj, L.FocalLoss) and isinstance(cl.BCEcls, L.FocalLoss)
+        pp = [x.clone().requires_grad_(True) for x in p]
+        loss, items = cl(pp, targets)
+        loss.backward()
+        d = {'meta': meta(hyp, nc, img), 'targets': npy(targets), 'anchors': npy(model.model[-1].anchors),
+             'loss': npy(loss), 'items': npy(items)}
+        for i in range(3):
+            d[f'p.{i}'] = npy(p[i])
+            d[f'gp.{i}'] = npy(pp[i].grad)
+        np.savez_compressed(os.path.join(OUT, f'focal_{name}.npz'), **d)
+        print('wrote focal', name, float(loss))
+
+    nc, img, ncall = 10, 128, 4
+    for name, gamma in [('autobalance', 1.5), ('autobalance_g0', 0.0)]:
+        model, hyp = _focal_model('VisDrone', nc, img, gamma)
+        targets = synth_targets(bs, 12, nc, seed=31)
+        cl = L.ComputeLoss(model, autobalance=True)
+        assert cl.ssi == 1
+        ps, losses, itemss, bals = [], [], [], []
+        for k in range(ncall):
+            p = [rnd(bs, 3, img // s, img // s, nc + 5, seed=30 + i + 10 * k) for i, s in enumerate((8, 16, 32))]
+            pp = [x.clone().requires_grad_(True) for x in p]
+            loss, items = cl(pp, targets)
+            ps.append(p)
+            losses.append(npy(loss))
+            itemss.append(npy(items))
+            bals.append(np.array(cl.balance, dtype=np.float64))
+        loss.backward()
+        d = {'meta': meta(hyp, nc, img, autobalance=True, ssi=cl.ssi, calls=ncall), 'targets': npy(targets),
+             'anchors': npy(model.model[-1].anchors), 'loss': np.stack(losses), 'items': np.stack(itemss),
+             'balance': np.stack(bals)}
+        for i in range(3):
+            d[f'p.{i}'] = np.stack([npy(ps[k][i]) for k in range(ncall)])
+            d[f'gp.{i}'] = npy(pp[i].grad)
+        np.savez_compressed(os.path.join(OUT, f'focal_{name}.npz'), **d)
+        print('wrote focal', name, bals[-1])
+
+
 def gen_siou():
     g = torch.Generator().manual_seed(40)
     n = 256
