@@ -172,7 +172,6 @@ struct Geom {
   // wgrad_split_reduce sums the splits in index order; null = fp32 atomics into dw
   float* dws;
   long dws_slab;
-  int* plan;            // non-null: only report the split count the dispatch would use (*plan), launch nothing
 };
 
 // weight-grad epilogue store: deterministic workspace slot of this split, or an fp32 atomic into dw
@@ -3463,7 +3462,7 @@ Geom make_geom(int N, int H, int W, int C, long xps, int K, int KH, int KW, int 
   g.N = N; g.H = H; g.W = W; g.C = C; g.K = K; g.KH = KH; g.KW = KW; g.S = S; g.P = P;
   g.OH = OH; g.OW = OW; g.xps = xps; g.yps = yps;
   g.oihw = 0; g.zeroed = 0;
-  g.dws = nullptr; g.dws_slab = 0; g.plan = nullptr;
+  g.dws = nullptr; g.dws_slab = 0;
   return g;
 }
 
@@ -3476,23 +3475,66 @@ __global__ void wgrad_split_reduce(const float* __restrict__ ws, float* __restri
   }
 }
 
-// Called by every weight-grad launcher once its split count is known.  Returns true when the caller must return
-// right away (plan query).  Deterministic mode with one split keeps the single atomic per element (exact: it adds
-// to a zero or to an earlier stream-ordered launch's value), so g.dws is dropped.
-inline bool wgrad_begin(Geom& g, int splits) {
-  if (g.plan != nullptr) {
-    *g.plan = splits;
-    return true;
-  }
-  if (g.dws != nullptr && splits <= 1) g.dws = nullptr;
-  return false;
-}
-inline void wgrad_end(const Geom& g, float* dw, int splits, hipStream_t st) {
-  if (g.dws != nullptr)
-    wgrad_split_reduce<<<grid_cap(ceil_div(g.dws_slab, 256), 2048), 256, 0, st>>>(g.dws, dw, g.dws_slab, splits);
-}
-
 inline bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
+inline bool is_p1(const Geom& g) { return g.KH == 1 && g.KW == 1 && g.S == 1 && g.P == 0; }
+// byte extents of the bf16 operands of g (H x W x C gather tensor, OH x OW x K output, K x KH x KW x C weights): the
+// num_records of their buffer descriptors, which must stay below the out-of-range offset v3::kBufOob
+inline double x_bytes(const Geom& g) { return 2.0 * ((double)g.N * g.H * g.W * g.xps); }
+inline double y_bytes(const Geom& g) { return 2.0 * ((double)g.N * g.OH * g.OW * g.yps); }
+inline double w_bytes(const Geom& g) { return 2.0 * g.K * g.KH * g.KW * g.C; }
+inline bool fits_buf(double bytes) { return bytes < (double)v3::kBufOob; }
+
+// ---------------------------------------------------------------- routing plans
+// One function decides which kernel a bf16 implicit-GEMM launch takes; the launch executes that plan and
+// dmy_conv_fwd_bn_rows reads the BN partial-row count off the same plan, so the two cannot drift (ADVICE r4).
+// The values are the DMY_KERN_* codes of include/dmayolo.h (dmy_conv_route): append, never renumber.
+enum class Kern {
+  // forward, and the stride-1 data-grad as a forward over its GEMM view (V2 = the 64 x 64 register-staged tile)
+  HALO, SPLITK, P1S, STEM, P1P, PIPE8, WIDE, WIDE288, TALL, V3, V2,
+  // data-grad: v2 128 x 128 tile; stride 2 as one GEMM (32 / 64-128 channels), four classes merged, one launch a class
+  V2_BIG, S2_Q2S, S2_Q2, S2_MERGED, S2_CLASS,
+  // weight-grad: tap-fused 128 / 64 / 64-row two-plane tiles, v4, v3, v3n with 128 / 256 columns, v2 128 / 64 tiles
+  W_TAP128, W_TAP64, W_TAP64X2, W_V4, W_V3, W_V3N128, W_V3N256, W_V2_128, W_V2_64
+};
+struct Plan {
+  Kern k;
+  bool buf;   // buffer-descriptor loader (C % 64 == 0, byte offsets < 4 GiB)
+  bool lane;  // P1P: per-lane BN partials, one row per wave of the persistent grid
+  long rows;  // BN partial rows the launch writes (when it writes them)
+};
+struct WPlan {
+  Kern k;
+  int splits, per;  // split-K over pixels: splits launches' worth of grid.y, per K steps each
+};
+
+// Split-K of a weight-grad over its nk K steps (pixels) for a grid of `tiles` output tiles: {splits, per} with per K
+// steps a split.  At least 8 steps per split; the sweep takes the first minimum of the cost model
+//   rounds(tiles * s / R) * (K steps per split) * t_step + tiles * s * t_atomic   [us]
+// with R resident blocks on the chip, t_step per K step of a block and t_atomic for a block's fp32 atomics.  Each
+// caller keeps the source of its three constants.
+inline WPlan wgrad_split(Kern k, int tiles, int nk, double R, double t_step, double t_atomic) {
+  int maxs = nk / 8;
+  if (maxs < 1) maxs = 1;
+  int splits = 1;
+  double best = 1e300;
+  for (int sp = 1; sp <= maxs; sp += (sp < 16 ? 1 : sp / 16)) {
+    const double blocks = (double)tiles * sp;
+    const double t = ceil(blocks / R) * ceil_div(nk, sp) * t_step + blocks * t_atomic;
+    if (t < best) { best = t; splits = sp; }
+  }
+  const int per = ceil_div(nk, splits);
+  return WPlan{k, ceil_div(nk, per), per};
+}
+// the v2 (register-staged) weight-grad's rule: aim for ~2048 blocks, >= 8 K-tiles per split
+inline WPlan wgrad_split_v2(Kern k, int tiles, int nk) {
+  int splits = 2048 / tiles;
+  if (splits < 1) splits = 1;
+  int maxs = nk / 8;
+  if (maxs < 1) maxs = 1;
+  if (splits > maxs) splits = maxs;
+  const int per = ceil_div(nk, splits);
+  return WPlan{k, ceil_div(nk, per), per};
+}
 
 // tile choice shared by launch and partial-row query
 // v2 (register-staged) tiles.  The BN partial-row numbering of every training forward (dmy_conv_fwd_partial_rows:
@@ -3510,7 +3552,7 @@ int launch_fwd(const T* x, const T* w, const float* b, T* y, float* ps, float* p
   constexpr int VW = Traits<T>::VW;
   const long M = (long)g.N * g.OH * g.OW;
   const int gm = ceil_div(M, BM), gn = ceil_div(g.K, BN);
-  const bool p1 = g.KH == 1 && g.KW == 1 && g.S == 1 && g.P == 0;
+  const bool p1 = is_p1(g);
   const bool vec = g.C % VW == 0 && g.xps % VW == 0 && aligned16(x);
   const unsigned grid = (unsigned)gm * gn;
   if (vec && p1) conv_fwd_kernel<T, BM, BN, true, true><<<grid, NT, 0, st>>>(x, w, b, y, ps, pq, g, gm, gn, ep);
@@ -3523,7 +3565,7 @@ int launch_fwd(const T* x, const T* w, const float* b, T* y, float* ps, float* p
 template <typename T, int BM, int BN>
 int launch_dgrad(const T* dy, const T* wt, T* dx, int acc, const Geom& g, hipStream_t st) {
   constexpr int VW = Traits<T>::VW;
-  const bool p1 = g.KH == 1 && g.KW == 1 && g.S == 1 && g.P == 0;
+  const bool p1 = is_p1(g);
   const bool s2 = g.S == 2;
   const long M = s2 ? (long)g.N * ((g.H + 1) / 2) * ((g.W + 1) / 2) : (long)g.N * g.H * g.W;
   const int gm = ceil_div(M, BM), gn = ceil_div(g.C, BN);
@@ -3540,32 +3582,17 @@ int launch_dgrad(const T* dy, const T* wt, T* dx, int acc, const Geom& g, hipStr
 }
 
 template <typename T, int BM, int BN>
-int launch_wgrad(const T* x, const T* dy, float* dw, Geom g, hipStream_t st) {
+void launch_wgrad(const T* x, const T* dy, float* dw, const Geom& g, hipStream_t st, const WPlan& pl) {
   constexpr int VW = Traits<T>::VW;
-  constexpr int BK = Cfg<T>::BK;
-  const long NP = (long)g.N * g.OH * g.OW;
   const int Ntot = g.KH * g.KW * g.C;
   const int gm = ceil_div(g.K, BM), gn = ceil_div(Ntot, BN);
-  const int nk = ceil_div(NP, BK);
-  // split-K over pixels: aim for ~2048 blocks, >= 8 K-tiles per split
-  int splits = 2048 / (gm * gn);
-  if (splits < 1) splits = 1;
-  int maxs = nk / 8;
-  if (maxs < 1) maxs = 1;
-  if (splits > maxs) splits = maxs;
-  const int per = ceil_div(nk, splits);
-  splits = ceil_div(nk, per);
-  const dim3 grid((unsigned)gm * gn, splits);
-  if (wgrad_begin(g, splits)) return 0;
+  const dim3 grid((unsigned)gm * gn, pl.splits);
   const bool va = g.K % VW == 0 && g.yps % VW == 0 && aligned16(dy);
   const bool vb = g.C % VW == 0 && g.xps % VW == 0 && aligned16(x);
-  if (!g.zeroed) (void)hipMemsetAsync(dw, 0, sizeof(float) * (size_t)g.K * Ntot, st);
-  if (va && vb) conv_wgrad_kernel<T, BM, BN, true, true><<<grid, NT, 0, st>>>(x, dy, dw, per, g, gm, gn);
-  else if (va) conv_wgrad_kernel<T, BM, BN, true, false><<<grid, NT, 0, st>>>(x, dy, dw, per, g, gm, gn);
-  else if (vb) conv_wgrad_kernel<T, BM, BN, false, true><<<grid, NT, 0, st>>>(x, dy, dw, per, g, gm, gn);
-  else conv_wgrad_kernel<T, BM, BN, false, false><<<grid, NT, 0, st>>>(x, dy, dw, per, g, gm, gn);
-  wgrad_end(g, dw, splits, st);
-  return (int)hipGetLastError();
+  if (va && vb) conv_wgrad_kernel<T, BM, BN, true, true><<<grid, NT, 0, st>>>(x, dy, dw, pl.per, g, gm, gn);
+  else if (va) conv_wgrad_kernel<T, BM, BN, true, false><<<grid, NT, 0, st>>>(x, dy, dw, pl.per, g, gm, gn);
+  else if (vb) conv_wgrad_kernel<T, BM, BN, false, true><<<grid, NT, 0, st>>>(x, dy, dw, pl.per, g, gm, gn);
+  else conv_wgrad_kernel<T, BM, BN, false, false><<<grid, NT, 0, st>>>(x, dy, dw, pl.per, g, gm, gn);
 }
 
 // v3 (LDS-DMA) kernels apply to bf16 with 16-B vectors everywhere and enough rows to fill the chip
@@ -3592,17 +3619,27 @@ inline int num_cus();
 // gpurun_out/r5/ab_w8p.log: C1024 -> K1024 @48^2 bs32 fwd 200 -> 175 us, dgrad 186 -> 161, C4096 -> K1024 fwd 592 ->
 // 526; every 3x3 shape within +-1.5 %, so those keep conv_fwd_w)
 constexpr int kWideMinCols = 256;
+// rows of the wide tile for k > 1 views of M rows and gn 256-column tiles: 256 or 288, whichever grid ends in fewer
+// row-weighted rounds of the chip.  A block per CU at a time, so a grid of 4.5 rounds (3x3 256 @96^2 bs32: 1152 tiles
+// of 256 rows) costs 5 and idles half the chip for the last; 288 = 9 x 32 divides every DMA-YOLO @1536 / config-5
+// @1920 map (1536^2 and 1920^2 carry a factor 9): 1024 tiles, 4 rounds of 288 rows = 1152 row-times against 1280.
+// (2.25 -> 2 rounds at 512 @48^2.)
+inline int wide_rows(long M, long gn) {
+  const long NC = num_cus();
+  const long t256 = ceil_div(ceil_div(M, 256) * gn, NC) * 256, t288 = ceil_div(ceil_div(M, 288) * gn, NC) * 288;
+  return t288 < t256 ? 288 : 256;
+}
 // tall 512 x 128 tiles (v3::conv_fwd_w) for k > 1 GEMM views with 65..128 columns and >= 4 blocks per CU: +4..8 % on
 // the 128-channel 3x3 layers of DMA-YOLO / config 5 (profiles/r02/ab_tall.log)
 // 1x1 streaming GEMM (v3::conv_p1s) for the output-heavy stride-1 1x1 forwards (>= 2x as many columns as reduction):
 // 1.05-1.38x the LDS-DMA tiles there (profiles/r02/ab_p1s.log); on the other 1x1 shapes those tiles already stream at
 // 4.5-6 TB/s and stay faster
 inline bool p1s_ok(const Geom& gv, const void* x, const void* w, const void* y) {
-  if (gv.KH != 1 || gv.KW != 1 || gv.S != 1 || gv.P != 0) return false;
+  if (!is_p1(gv)) return false;
   if (gv.C != 64 && gv.C != 128 && gv.C != 256) return false;
   if (gv.K % 32 != 0 || gv.xps % 8 != 0 || gv.yps % 8 != 0 || !aligned16(x) || !aligned16(w) || !aligned16(y))
     return false;
-  return 2.0 * ((double)gv.N * gv.OH * gv.OW * gv.xps) < (double)v3::kBufOob;
+  return fits_buf(2.0 * ((double)gv.N * gv.OH * gv.OW * gv.xps));
 }
 // threads per block of the training stem: 512 = 64-column passes that write whole 128-B output lines per pixel, for
 // >= 64 output channels; 768 = 32-column passes otherwise.  Cold-cache (profiles/r04/stem_ab.log): DMA-1536 stem (64 ch
@@ -3614,7 +3651,7 @@ inline bool stem_s_ok(const Geom& gv, const void* x, const void* w, const void* 
   if (gv.C != 16 || gv.KH != 3 || gv.KW != 3 || gv.S != 1 || gv.P != 1 || gv.OH != gv.H || gv.OW != gv.W) return false;
   if (gv.K % 32 != 0 || gv.K > 256 || gv.xps % 8 != 0 || gv.yps % 8 != 0 || !aligned16(x) || !aligned16(w) || !aligned16(y))
     return false;
-  return 2.0 * ((double)gv.N * gv.H * gv.W * gv.xps) < (double)v3::kBufOob && (long)gv.N * gv.H * gv.W < (1L << 31);
+  return fits_buf(x_bytes(gv)) && (long)gv.N * gv.H * gv.W < (1L << 31);
 }
 // column groups of a streaming-GEMM launch (conv_p1s, 512 threads, 160 KiB of LDS): each group holds ng columns of W
 // in LDS and streams every X row again
@@ -3643,7 +3680,7 @@ int launch_p1s_kd(const bf16* x, const bf16* w, const float* b, bf16* y, float* 
   const int maxb = ceil_div(ntiles, NTH / 64);
   if (nbx > maxb) nbx = maxb;
   const dim3 grid((unsigned)nbx, (unsigned)G);
-  const double xb = 2.0 * ((double)gv.N * gv.H * gv.W * gv.xps);
+  const double xb = x_bytes(gv);
   v3::conv_p1s<KD, NTH, G3, DG><<<grid, NTH, lds, st>>>(x, w, b, y, ps, pq, acc, M, gv.K, ng, gv.xps, gv.yps, (unsigned)xb,
                                                ntiles, gv.KH * gv.KW * gv.C, gv.H, gv.W);
   return (int)hipGetLastError();
@@ -3683,7 +3720,7 @@ int p1p_plan(const Geom& gv, int acc, const Epi& ep, F&& f) {
   const int nk = gv.C / v3::BK;
   const double yb = 2.0 * ((double)(M - 1) * gv.yps + gv.K);
   const double rb = ep.res != nullptr ? 2.0 * ((double)(M - 1) * ep.rps + gv.K) : 0.0;
-  if (acc || gv.K % 8 != 0 || yb >= (double)v3::kBufOob || rb >= (double)v3::kBufOob || nk < 1 ||
+  if (acc || gv.K % 8 != 0 || !fits_buf(yb) || !fits_buf(rb) || nk < 1 ||
       (ep.res != nullptr && (ep.rps % 8 != 0 || !aligned16(ep.res))) || gv.K > kP1pMaxCols)
     return -1;
   // 129..256 columns over a >= 1024-deep reduction: the 256 x 256 half-tile pipeline reads each input row once and
@@ -3735,16 +3772,16 @@ int launch_p1p(const bf16* x, const bf16* w, const float* b, bf16* y, float* ps,
   });
 }
 
-// 3x3 stride-1 64 -> 64-channel layers on the persistent halo kernel (v3::conv3_halo64).  g = the GEMM view (gathered H x W x C with pixel stride xps, output OH x OW x K with stride yps); whole 8 x 32
-// output tiles only, at least one tile per CU, no bias / inference epilogue (the callers check those).
+// 3x3 stride-1 64 -> 64-channel layers on the persistent halo kernel (v3::conv3_halo64).  g = the GEMM view (gathered
+// H x W x C with pixel stride xps, output OH x OW x K with stride yps); whole 8 x 32 output tiles only, at least one
+// tile per CU, no bias / inference epilogue (the callers check those).
 inline long halo_units(const Geom& g) { return (long)g.N * (g.H / v3::halo::TH) * (g.W / v3::halo::TW); }
 inline bool halo_ok(const Geom& g, const void* x, const void* w, const void* y) {
   if (g.KH != 3 || g.KW != 3 || g.S != 1 || g.P != 1 || g.C != 64 || g.K != 64 ||
       g.OH != g.H || g.OW != g.W || g.H % v3::halo::TH != 0 || g.W % v3::halo::TW != 0 || g.xps % 8 != 0 ||
       g.yps % 8 != 0 || !aligned16(x) || !aligned16(w) || !aligned16(y))
     return false;
-  const double xb = 2.0 * ((double)g.N * g.H * g.W * g.xps), yb = 2.0 * ((double)g.N * g.OH * g.OW * g.yps);
-  return xb < (double)v3::kBufOob && yb < (double)v3::kBufOob && halo_units(g) >= num_cus();
+  return fits_buf(x_bytes(g)) && fits_buf(y_bytes(g)) && halo_units(g) >= num_cus();
 }
 // persistent grid: per = tiles per block, every block gets at least one (so every BN partial row is written)
 inline int halo_blocks(const Geom& g, int* per_out = nullptr) {
@@ -3761,8 +3798,7 @@ int launch_halo(const bf16* x, const bf16* w, bf16* y, float* ps, float* pq, con
   const int thn = g.H / v3::halo::TH, twn = g.W / v3::halo::TW, nt = (int)halo_units(g);
   int per = 1;
   const int G = halo_blocks(g, &per);
-  const unsigned xb = (unsigned)(2.0 * ((double)g.N * g.H * g.W * g.xps));
-  const unsigned yb = (unsigned)(2.0 * ((double)g.N * g.OH * g.OW * g.yps));
+  const unsigned xb = (unsigned)x_bytes(g), yb = (unsigned)y_bytes(g);
   const unsigned rb = ep.res != nullptr ? (unsigned)(2.0 * ((double)g.N * g.OH * g.OW * ep.rps)) : 0u;
   if (!DG && ep.on)  // inference epilogue: its own instantiation, so the training kernel's registers are untouched
     v3::conv3_halo64<false, true><<<(unsigned)G, 64 * v3::halo::NW, 0, st>>>(x, w, y, ps, pq, g, twn, thn, nt, per,
@@ -3773,21 +3809,11 @@ int launch_halo(const bf16* x, const bf16* w, bf16* y, float* ps, float* pq, con
   return (int)hipGetLastError();
 }
 
-// ---------------------------------------------------------------- routing plans
-// One function decides which kernel a bf16 implicit-GEMM launch takes; the launch executes that plan and
-// dmy_conv_fwd_bn_rows reads the BN partial-row count off the same plan, so the two cannot drift (ADVICE r4).
-enum class Kern { HALO, SPLITK, P1S, STEM, P1P, PIPE8, WIDE, WIDE288, TALL, V3, V2 };
-struct Plan {
-  Kern k;
-  bool buf;   // buffer-descriptor loader (C % 64 == 0, byte offsets < 4 GiB)
-  bool lane;  // P1P: per-lane BN partials, one row per wave of the persistent grid
-  long rows;  // BN partial rows the launch writes (when it writes them)
-};
 // the v3 family for GEMM view gv (forward, or data-grad when DG)
 template <bool DG>
 Plan plan_v3(const Geom& gv, const void* x, const void* w, const void* y, int acc, const Epi& ep) {
   const long M = (long)gv.N * gv.OH * gv.OW;
-  const bool p1 = gv.KH == 1 && gv.KW == 1 && gv.S == 1 && gv.P == 0;
+  const bool p1 = is_p1(gv);
   Plan pl{Kern::V3, false, false, dmy_conv_fwd_partial_rows(M, gv.K)};
   // output-heavy 1x1 data-grads (dx channels >= 2 x dy channels) on the streaming GEMM too, when W fits <= 4 column
   // groups (profiles/r06/p1sdg_ab.log, cold caches: 512 <- 128 @192^2 bs32 465 -> 355 us, 1024 <- 256 @96^2 269 -> 230;
@@ -3798,8 +3824,7 @@ Plan plan_v3(const Geom& gv, const void* x, const void* w, const void* y, int ac
     if (p1s_ok(gv, x, w, y) && gv.K >= 2 * gv.C) return pl.k = Kern::P1S, pl;  // output-heavy 1x1: streaming GEMM
     if (stem_s_ok(gv, x, w, y)) return pl.k = Kern::STEM, pl;  // the 16-channel 3x3 stem view (p1s, G3 gather)
   }
-  const double xb = 2.0 * ((double)gv.N * gv.H * gv.W * gv.xps), wb = 2.0 * gv.K * gv.KH * gv.KW * gv.C;
-  pl.buf = gv.C % 64 == 0 && xb < (double)v3::kBufOob && wb < (double)v3::kBufOob;
+  pl.buf = gv.C % 64 == 0 && fits_buf(x_bytes(gv)) && fits_buf(w_bytes(gv));
   if (p1 && pl.buf && !ep.on && p1p_plan<DG>(gv, acc, ep, [](auto, auto, auto, auto) { return 0; }) >= 0) {
     pl.k = Kern::P1P;  // persistent 1x1 with the register epilogue
     if (!DG) {
@@ -3814,13 +3839,8 @@ Plan plan_v3(const Geom& gv, const void* x, const void* w, const void* y, int ac
     // @1536 4.25 -> 4.19 ms, profiles/r06/ep8_ab.log)
     if (p1 && ep.on && gv.C <= 128) return pl;
     if (p1) return pl.k = Kern::PIPE8, pl;
-    // k > 1: 256- or 288-row tiles, whichever grid ends in fewer row-weighted rounds of the chip.  A block per CU at a
-    // time, so a grid of 4.5 rounds (3x3 256 @96^2 bs32: 1152 tiles of 256 rows) costs 5 and idles half the chip for
-    // the last; 288 = 9 x 32 divides every DMA-YOLO @1536 / config-5 @1920 map (1536^2 and 1920^2 carry a factor 9):
-    // 1024 tiles, 4 rounds of 288 rows = 1152 row-times against 1280.  (2.25 -> 2 rounds at 512 @48^2.)
-    const long gn = ceil_div(gv.K, 256), NC = num_cus();
-    const long t256 = ceil_div(ceil_div(M, 256) * gn, NC) * 256, t288 = ceil_div(ceil_div(M, 288) * gn, NC) * 288;
-    if (t288 < t256) {
+    // k > 1: 256- or 288-row tiles (wide_rows)
+    if (wide_rows(M, ceil_div(gv.K, 256)) == 288) {
       pl.k = Kern::WIDE288;
       pl.rows = ceil_div(M, 288) * 2;  // one BN partial row per wave row (2) and row tile
       return pl;
@@ -3835,9 +3855,8 @@ template <bool DG>
 int launch_v3(const bf16* x, const bf16* w, const float* b, bf16* y, float* ps, float* pq, int acc, const Geom& gv,
               hipStream_t st, const Epi& ep, const Plan& pl) {
   const long M = (long)gv.N * gv.OH * gv.OW;
-  const bool p1 = gv.KH == 1 && gv.KW == 1 && gv.S == 1 && gv.P == 0;
-  const double xb = 2.0 * ((double)gv.N * gv.H * gv.W * gv.xps), wb = 2.0 * gv.K * gv.KH * gv.KW * gv.C;
-  const unsigned xbytes = pl.buf ? (unsigned)xb : 0u, wbytes = pl.buf ? (unsigned)wb : 0u;
+  const bool p1 = is_p1(gv);
+  const unsigned xbytes = pl.buf ? (unsigned)x_bytes(gv) : 0u, wbytes = pl.buf ? (unsigned)w_bytes(gv) : 0u;
 #define W_GO(BM, BN)                                                                                                 \
   {                                                                                                                  \
     const int gm = ceil_div(M, BM), gn = ceil_div(gv.K, BN);                                                         \
@@ -3917,8 +3936,7 @@ inline int splitk_plan(const Geom& g, const void* x, const void* w, const void* 
   if (M >= 16384 || M == 0 || g.C % 64 != 0 || g.xps % 8 != 0 || g.K % 8 != 0 || g.yps % 8 != 0 || g.K < 32 ||
       !aligned16(x) || !aligned16(w) || !aligned16(y))
     return 0;
-  const double xb = 2.0 * ((double)g.N * g.H * g.W * g.xps), wb = 2.0 * g.K * g.KH * g.KW * g.C;
-  if (xb >= (double)v3::kBufOob || wb >= (double)v3::kBufOob) return 0;
+  if (!fits_buf(x_bytes(g)) || !fits_buf(w_bytes(g))) return 0;
   // detect-path A/B (profiles/r02/det_splitk.log): target 2 blocks per CU, at least 2 K steps per split; 1x1 layers
   // stay unsplit (their fp32 slabs + the reduce pass cost more than the split gains; bs1 detect DMA-1536 6.68 -> 6.45
   // ms, yolov5s 1.035 -> 0.968 ms)
@@ -3946,8 +3964,8 @@ inline int launch_splitk(const bf16* x, const bf16* w, const float* b, bf16* y, 
   int gm, gn, per;
   const int sp = splitk_plan(g, x, w, y, gm, gn, per);
   const long M = (long)g.N * g.OH * g.OW;
-  const unsigned xb = (unsigned)(2.0 * ((double)g.N * g.H * g.W * g.xps)), wb = (unsigned)(2.0 * g.K * g.KH * g.KW * g.C);
-  const bool p1 = g.KH == 1 && g.KW == 1 && g.S == 1 && g.P == 0;
+  const unsigned xb = (unsigned)x_bytes(g), wb = (unsigned)w_bytes(g);
+  const bool p1 = is_p1(g);
   const dim3 grid((unsigned)gm * gn, (unsigned)sp);
   if (g.K > 64) {
     if (p1) v3::conv_fwd_split<128, 128, 2, true><<<grid, 256, 0, st>>>(x, w, ws, g, gm, gn, per, xb, wb);
@@ -3967,7 +3985,7 @@ Plan plan_fwd(const Geom& g, const void* x, const void* w, const float* b, const
   const bool res_ok = !ep.res || (ep.rps % 8 == 0 && aligned16(ep.res));
   if (b == nullptr && halo_ok(g, x, w, y) && (!ep.on || !bn) && halo_rows(g) <= prow_persist_cap() &&
       (!ep.on || ep.res == nullptr ||
-       (res_ok && 2.0 * ((double)g.N * g.OH * g.OW * ep.rps) < (double)v3::kBufOob)))
+       (res_ok && fits_buf(2.0 * ((double)g.N * g.OH * g.OW * ep.rps)))))
     return Plan{Kern::HALO, true, false, halo_rows(g)};  // one BN partial row per wave
   if (ws_elems > 0 && !bn && res_ok) {
     const long need = splitk_elems(g, x, w, y);
@@ -3996,45 +4014,67 @@ int conv_fwd_t(const void* x, const void* w, const float* b, void* y, float* ps,
     return launch_fwd<T, 128, 128>((const T*)x, (const T*)w, b, (T*)y, ps, pq, g, st, ep);
   return launch_fwd<T, 64, 64>((const T*)x, (const T*)w, b, (T*)y, ps, pq, g, st, ep);
 }
-// stride-2 data-grad on the v3 buffer loader: one launch per output-parity class (a, b), each a GEMM
-// over the class's input pixels and only the taps of matching parity (FwdLdsB S2 mode)
-inline bool dgrad_s2_v3_ok(const Geom& g, const void* dy, const void* wt, const void* dx) {
-  if (g.S != 2 || g.K % 64 != 0 || g.KH < 2 || g.KW < 2) return false;
-  const long Mmin = (long)g.N * (g.H / 2) * (g.W / 2);
-  const double xb = 2.0 * ((double)g.N * g.OH * g.OW * g.yps), wb = 2.0 * g.C * g.KH * g.KW * g.K;
-  return v3_ok(g.K, g.yps, g.C, g.xps, dy, wt, dx, Mmin) && xb < (double)v3::kBufOob && wb < (double)v3::kBufOob;
+// ---------------------------------------------------------------- data-grad
+// stride-1 data-grad as a forward over its GEMM view: rows = input pixels (N, H, W), columns = C, gather dy
+// (OH x OW x K, stride yps)
+inline Geom dgrad_view(const Geom& g) {
+  return make_geom(g.N, g.OH, g.OW, g.K, g.yps, g.C, g.KH, g.KW, 1, g.P, g.H, g.W, g.xps);
 }
-// the one-GEMM form (v3::conv_dgrad_q2 / _q2s) for 32 / 64 / 128 input channels, 3x3 stride 2 pad 1, a grid of >= one
-// 256-row tile per CU.  32 channels, against the merged four-class launch (profiles/r06/q2s_ab.log): 32 <- 64 @320^2
-// bs64 (yolov5s) 462 -> 290 us, @384^2 bs32 318 -> 198, @640^2 bs16 436 -> 262; yolov5s step 16.60 -> 16.42 ms.  128 channels, against the four 256 x 128 class launches (profiles/r06/q2h_ab.log): 128 <- 256 @384^2 bs32
-// 1318 -> 1207 us, @80^2 bs64 127 -> 103, @480^2 bs8 545 -> 460
-inline bool dgrad_q2_ok(const Geom& g) {
-  if (g.C != 32 && g.C != 64 && g.C != 128) return false;
-  return g.KH == 3 && g.KW == 3 && g.P == 1 && g.S == 2 && g.K % 64 == 0 &&
-         g.OH == (g.H + 1) / 2 && g.OW == (g.W + 1) / 2 && g.xps % 8 == 0 &&
-         ceil_div((long)g.N * g.OH * g.OW, 256) >= num_cus();
+// the v2 (register-staged) data-grad: 128 x 128 tiles when that grid fills the chip (big_tile), else 64 x 64
+inline Plan plan_dgrad_v2(const Geom& g) {
+  const long M = (long)g.N * g.H * g.W / (g.S == 2 ? 4 : 1);
+  return Plan{big_tile(M, g.C) ? Kern::V2_BIG : Kern::V2, false, false, 0};
 }
-inline int launch_dgrad_s2_v3(const bf16* dy, const bf16* wt, bf16* dx, int acc, const Geom& g, hipStream_t st) {
-  const unsigned xbytes = (unsigned)(2.0 * ((double)g.N * g.OH * g.OW * g.yps));
-  const unsigned wbytes = (unsigned)(2.0 * g.C * g.KH * g.KW * g.K);
-  if (dgrad_q2_ok(g)) {
-    const Geom gq = make_geom(g.N, g.OH, g.OW, g.K, g.yps, 256, 2, 2, 1, 0, g.OH, g.OW, g.xps);
+// the bf16 data-grad's plan
+Plan plan_dgrad(const Geom& g, const void* dy, const void* wt, const void* dx, int acc) {
+  // stride 2 on the v3 buffer loader: every launch gathers dy (OH x OW x K) and the IHWO weights through buffer
+  // descriptors, so both extents stay below kBufOob, with 16-B vectors everywhere and enough rows in the smallest
+  // parity class (v3_ok)
+  if (g.S == 2 && g.K % 64 == 0 && g.KH >= 2 && g.KW >= 2 &&
+      v3_ok(g.K, g.yps, g.C, g.xps, dy, wt, dx, (long)g.N * (g.H / 2) * (g.W / 2)) && fits_buf(y_bytes(g)) &&
+      fits_buf(w_bytes(g))) {
+    Plan pl{Kern::S2_CLASS, true, false, 0};
+    // the one-GEMM form (v3::conv_dgrad_q2 / _q2s) for 32 / 64 / 128 input channels, 3x3 stride 2 pad 1, a grid of >=
+    // one 256-row tile per CU.  32 channels, against the merged four-class launch (profiles/r06/q2s_ab.log): 32 <- 64
+    // @320^2 bs64 (yolov5s) 462 -> 290 us, @384^2 bs32 318 -> 198, @640^2 bs16 436 -> 262; yolov5s step 16.60 -> 16.42
+    // ms.  128 channels, against the four 256 x 128 class launches (profiles/r06/q2h_ab.log): 128 <- 256 @384^2 bs32
+    // 1318 -> 1207 us, @80^2 bs64 127 -> 103, @480^2 bs8 545 -> 460
+    if ((g.C == 32 || g.C == 64 || g.C == 128) && g.KH == 3 && g.KW == 3 && g.P == 1 && g.OH == (g.H + 1) / 2 &&
+        g.OW == (g.W + 1) / 2 && ceil_div((long)g.N * g.OH * g.OW, 256) >= num_cus())
+      return pl.k = g.C == 32 ? Kern::S2_Q2S : Kern::S2_Q2, pl;
+    // one launch for the four classes of <= 64-channel data-grads, one per class above.  Measured
+    // (profiles/r02/ab_s2_merge.log): +4..14 % at 32 / 64 channels, 16-33 % slower on the 1-block-per-CU 256 x 128
+    // tiles of the 128 / 256-channel layers, where the per-class launches stay.  The persistent class kernel (conv_s2p,
+    // round 5) was slower on every DMA-1536 shape (its A/B log is cited in the routing header above) and is gone.
+    if (g.C <= 64) return pl.k = Kern::S2_MERGED, pl;
+    return pl;
+  }
+  const long M = (long)g.N * g.H * g.W;
+  if (g.S == 1 && g.OH == g.H + 2 * g.P - g.KH + 1 && g.OW == g.W + 2 * g.P - g.KW + 1 &&
+      v3_ok(g.K, g.yps, g.C, g.xps, dy, wt, dx, M)) {
+    const Geom gv = dgrad_view(g);
+    if (halo_ok(gv, dy, wt, dx)) return Plan{Kern::HALO, true, false, 0};
+    return plan_v3<true>(gv, dy, wt, dx, acc, Epi{});
+  }
+  return plan_dgrad_v2(g);
+}
+
+// stride-2 data-grad on the v3 buffer loader (plan_dgrad's S2_* kinds): one GEMM over dy pixels, the four output-parity
+// classes (a, b) in one launch, or one launch per class, each a GEMM over the class's input pixels and only the taps
+// of matching parity (FwdLdsB S2 mode)
+inline int launch_dgrad_s2(const bf16* dy, const bf16* wt, bf16* dx, int acc, const Geom& g, hipStream_t st, Kern k) {
+  const unsigned xbytes = (unsigned)y_bytes(g), wbytes = (unsigned)w_bytes(g);
+  if (k == Kern::S2_Q2S || k == Kern::S2_Q2) {
     const int gm = (int)ceil_div((long)g.N * g.OH * g.OW, 256);
-    if (g.C == 32) {
-      const Geom gs = make_geom(g.N, g.OH, g.OW, g.K, g.yps, 128, 2, 2, 1, 0, g.OH, g.OW, g.xps);
-      v3::conv_dgrad_q2s<<<(unsigned)gm, 512, 0, st>>>(dy, wt, dx, acc, gs, gm, xbytes, wbytes, v3::S2Cls{0, 0, g.H, g.W});
-    } else if (g.C == 64)
-      v3::conv_dgrad_q2<64><<<(unsigned)gm, 512, 0, st>>>(dy, wt, dx, acc, gq, gm, xbytes, wbytes, v3::S2Cls{0, 0, g.H, g.W});
-    else
-      v3::conv_dgrad_q2<128><<<(unsigned)(2 * gm), 512, 0, st>>>(dy, wt, dx, acc, gq, gm, xbytes, wbytes,
-                                                                 v3::S2Cls{0, 0, g.H, g.W});
+    // GEMM view: rows = dy pixels, the 2 x 2 dy window as taps, columns = classes x channels
+    const Geom gq = make_geom(g.N, g.OH, g.OW, g.K, g.yps, g.C == 32 ? 128 : 256, 2, 2, 1, 0, g.OH, g.OW, g.xps);
+    const v3::S2Cls c0{0, 0, g.H, g.W};
+    if (g.C == 32) v3::conv_dgrad_q2s<<<(unsigned)gm, 512, 0, st>>>(dy, wt, dx, acc, gq, gm, xbytes, wbytes, c0);
+    else if (g.C == 64) v3::conv_dgrad_q2<64><<<(unsigned)gm, 512, 0, st>>>(dy, wt, dx, acc, gq, gm, xbytes, wbytes, c0);
+    else v3::conv_dgrad_q2<128><<<(unsigned)(2 * gm), 512, 0, st>>>(dy, wt, dx, acc, gq, gm, xbytes, wbytes, c0);
     return (int)hipGetLastError();
   }
-  // one launch for the four classes of <= 64-channel data-grads, one per class above.  Measured
-  // (profiles/r02/ab_s2_merge.log): +4..14 % at 32 / 64 channels, 16-33 % slower on the 1-block-per-CU 256 x 128 tiles
-  // of the 128 / 256-channel layers, where the per-class launches stay.  The persistent class kernel (conv_s2p, round 5)
-  // was slower on every DMA-1536 shape (gpurun_out/r5/ab_s2p.log) and is gone.
-  if (g.C <= 64) {
+  if (k == Kern::S2_MERGED) {
     const long Mmax = (long)g.N * ((g.H + 1) / 2) * ((g.W + 1) / 2);  // class (0, 0) has the most rows
     const int gmax = ceil_div(Mmax, 256), gn = ceil_div(g.C, 64);
     v3::conv_dgrad_s2_v3<256, 64, 2><<<(unsigned)(4 * gmax * gn), 256, 0, st>>>(dy, wt, dx, acc, g, gmax, gn, xbytes,
@@ -4045,7 +4085,7 @@ inline int launch_dgrad_s2_v3(const bf16* dy, const bf16* wt, bf16* dx, int acc,
     for (int b = 0; b < 2; ++b) {
       const int H2 = (g.H - a + 1) / 2, W2 = (g.W - b + 1) / 2;
       if (H2 <= 0 || W2 <= 0) continue;
-      // GEMM view: gather dy (OH x OW x K, stride yps), rows = the class's (N, H2, W2), columns = C
+      // GEMM view: gather dy (OH x OW x K, stride yps), rows = the class's (N, H2, W2), columns = C (> 64 here)
       const Geom gv = make_geom(g.N, g.OH, g.OW, g.K, g.yps, g.C, g.KH, g.KW, 2, g.P, H2, W2, g.xps);
       const long M = (long)g.N * H2 * W2;
       const v3::S2Cls cls{a, b, g.H, g.W};
@@ -4055,9 +4095,7 @@ inline int launch_dgrad_s2_v3(const bf16* dy, const bf16* wt, bf16* dx, int acc,
       // measured 1228 -> 1257 and is not used)
       if (g.C % 256 == 0 && (long)ceil_div(M, 256) * (g.C / 256) >= num_cus()) {
         const int gn = g.C / 256;
-        const long NC = num_cus();
-        // 288-row tiles when their grid ends in fewer row-weighted rounds of the chip (plan_v3's rule)
-        if (ceil_div(ceil_div(M, 288) * gn, NC) * 288 < ceil_div(ceil_div(M, 256) * gn, NC) * 256) {
+        if (wide_rows(M, gn) == 288) {
           const int gm = ceil_div(M, 288);
           v3::conv_dgrad_s2_w<288, 256><<<(unsigned)gm * gn, 512, 0, st>>>(dy, wt, dx, acc, gv, gm, gn, xbytes, wbytes,
                                                                             cls);
@@ -4066,13 +4104,9 @@ inline int launch_dgrad_s2_v3(const bf16* dy, const bf16* wt, bf16* dx, int acc,
           v3::conv_dgrad_s2_w<256, 256><<<(unsigned)gm * gn, 512, 0, st>>>(dy, wt, dx, acc, gv, gm, gn, xbytes, wbytes,
                                                                             cls);
         }
-      } else if (g.C > 64) {
+      } else {
         const int gm = ceil_div(M, 256), gn = ceil_div(g.C, 128);
         v3::conv_fwd_v3<256, 128, 3, false, true, 3><<<(unsigned)gm * gn, 512, 0, st>>>(
-            dy, wt, nullptr, dx, nullptr, nullptr, acc, gv, gm, gn, xbytes, wbytes, cls, Epi{});
-      } else {
-        const int gm = ceil_div(M, 256), gn = ceil_div(g.C, 64);
-        v3::conv_fwd_v3<256, 64, 2, false, true, 3><<<(unsigned)gm * gn, 256, 0, st>>>(
             dy, wt, nullptr, dx, nullptr, nullptr, acc, gv, gm, gn, xbytes, wbytes, cls, Epi{});
       }
     }
@@ -4081,21 +4115,22 @@ inline int launch_dgrad_s2_v3(const bf16* dy, const bf16* wt, bf16* dx, int acc,
 
 template <typename T>
 int conv_dgrad_t(const void* dy, const void* wt, void* dx, int acc, const Geom& g, hipStream_t st) {
-  const long M = (long)g.N * g.H * g.W / (g.S == 2 ? 4 : 1);
+  Plan pl = plan_dgrad_v2(g);
   if constexpr (sizeof(T) == 2) {
-    if (dgrad_s2_v3_ok(g, dy, wt, dx))
-      return launch_dgrad_s2_v3((const bf16*)dy, (const bf16*)wt, (bf16*)dx, acc, g, st);
-    if (g.S == 1 && g.OH == g.H + 2 * g.P - g.KH + 1 && g.OW == g.W + 2 * g.P - g.KW + 1 &&
-        v3_ok(g.K, g.yps, g.C, g.xps, dy, wt, dx, M)) {
-      // GEMM view: rows = input pixels (N, H, W), columns = C, gather dy (OH x OW x K, stride yps)
-      Geom gv = make_geom(g.N, g.OH, g.OW, g.K, g.yps, g.C, g.KH, g.KW, 1, g.P, g.H, g.W, g.xps);
-      if (halo_ok(gv, dy, wt, dx))
-        return launch_halo<true>((const bf16*)dy, (const bf16*)wt, (bf16*)dx, nullptr, nullptr, gv, st, acc);
-      return launch_v3<true>((const bf16*)dy, (const bf16*)wt, nullptr, (bf16*)dx, nullptr, nullptr, acc, gv, st,
-                             Epi{}, plan_v3<true>(gv, dy, wt, dx, acc, Epi{}));
+    pl = plan_dgrad(g, dy, wt, dx, acc);
+    const bf16 *a = (const bf16*)dy, *b = (const bf16*)wt;
+    switch (pl.k) {
+      case Kern::V2:
+      case Kern::V2_BIG: break;
+      case Kern::S2_Q2S:
+      case Kern::S2_Q2:
+      case Kern::S2_MERGED:
+      case Kern::S2_CLASS: return launch_dgrad_s2(a, b, (bf16*)dx, acc, g, st, pl.k);
+      case Kern::HALO: return launch_halo<true>(a, b, (bf16*)dx, nullptr, nullptr, dgrad_view(g), st, acc);
+      default: return launch_v3<true>(a, b, nullptr, (bf16*)dx, nullptr, nullptr, acc, dgrad_view(g), st, Epi{}, pl);
     }
   }
-  if (big_tile(M, g.C)) return launch_dgrad<T, 128, 128>((const T*)dy, (const T*)wt, (T*)dx, acc, g, st);
+  if (pl.k == Kern::V2_BIG) return launch_dgrad<T, 128, 128>((const T*)dy, (const T*)wt, (T*)dx, acc, g, st);
   return launch_dgrad<T, 64, 64>((const T*)dy, (const T*)wt, (T*)dx, acc, g, st);
 }
 inline int num_cus() {
@@ -4108,85 +4143,14 @@ inline int num_cus() {
   return n;
 }
 
-inline int launch_wgrad_v3(const bf16* x, const bf16* dy, float* dw, Geom g, hipStream_t st) {
-  const long NP = (long)g.N * g.OH * g.OW;
-  const int Ntot = g.KH * g.KW * g.C;
-  const int gm = ceil_div(g.K, 128), gn = ceil_div(Ntot, 128);
-  const int nk = ceil_div(NP, 64);
-  // split-K over pixels.  Cost model (calibrated on MI355X): resident blocks R = 2 per CU; time ~
-  // rounds(tiles*s / R) * (K steps per split) * 1.9 us + tiles*s * 64 KiB of fp32 atomics at 1.3 TB/s.  It beat fixed
-  // 512 / 768-block targets on DMA-1536 (152.15 vs 150.76 / 147.91 img/s, profiles/r04/wgrad_target_ab.log)
-  const int tiles = gm * gn;
-  int maxs = nk / 8;
-  if (maxs < 1) maxs = 1;
-  int splits = 1;
-  {
-    const double R = 2.0 * num_cus();
-    double best = 1e300;
-    for (int sp = 1; sp <= maxs; sp += (sp < 16 ? 1 : sp / 16)) {
-      const double blocks = (double)tiles * sp;
-      const double t = ceil(blocks / R) * ceil_div(nk, sp) * 1.9 + blocks * 0.0504;
-      if (t < best) { best = t; splits = sp; }
-    }
-  }
-  if (splits > maxs) splits = maxs;
-  const int per = ceil_div(nk, splits);
-  splits = ceil_div(nk, per);
-  const dim3 grid((unsigned)gm * gn, splits);
-  if (wgrad_begin(g, splits)) return 0;
-  if (!g.zeroed) (void)hipMemsetAsync(dw, 0, sizeof(float) * (size_t)g.K * Ntot, st);
-  const double xb = 2.0 * ((double)g.N * g.H * g.W * g.xps), db = 2.0 * ((double)NP * g.yps);
-  const bool buf = xb < (double)v3::kBufOob && db < (double)v3::kBufOob;
-  if (buf)
-    v3::conv_wgrad_v3<2, 1><<<grid, 256, 0, st>>>(x, dy, dw, per, g, gm, gn, (unsigned)xb, (unsigned)db);
-  else
-    v3::conv_wgrad_v3<2, 0><<<grid, 256, 0, st>>>(x, dy, dw, per, g, gm, gn, 0u, 0u);
-  wgrad_end(g, dw, splits, st);
-  return (int)hipGetLastError();
-}
-
-// wgrad v4 tile 256 x 128 for K_out >= 256, else the v3 128 x 128 kernel (tools/gpu/ab_conv.sh,
-// profiles/r01/ab_wgrad_v4.log: +7-11 % at K_out >= 256, the 256-row tile is half idle and a 128 x 256 one no faster at
-// K_out = 128)
-template <int BM, int BN>
-int launch_wgrad_v4(const bf16* x, const bf16* dy, float* dw, Geom g, hipStream_t st) {
-  const long NP = (long)g.N * g.OH * g.OW;
-  const int Ntot = g.KH * g.KW * g.C;
-  const int gm = ceil_div(g.K, BM), gn = ceil_div(Ntot, BN);
-  const int nk = ceil_div(NP, 64);
-  const int tiles = gm * gn;
-  int maxs = nk / 8;
-  if (maxs < 1) maxs = 1;
-  int splits = 1;
-  {
-    // launch_wgrad_v3's model with one resident block per CU, twice the tile per K step and atomics
-    const double R = num_cus(), sc = (double)BM * BN / (256.0 * 128.0);
-    double best = 1e300;
-    for (int sp = 1; sp <= maxs; sp += (sp < 16 ? 1 : sp / 16)) {
-      const double blocks = (double)tiles * sp;
-      const double t = ceil(blocks / R) * ceil_div(nk, sp) * 1.9 * 2 * 0.5 * sc + blocks * 0.0504 * 2 * sc;
-      if (t < best) { best = t; splits = sp; }
-    }
-  }
-  if (splits > maxs) splits = maxs;
-  const int per = ceil_div(nk, splits);
-  splits = ceil_div(nk, per);
-  const dim3 grid((unsigned)tiles, splits);
-  if (wgrad_begin(g, splits)) return 0;
-  if (!g.zeroed) (void)hipMemsetAsync(dw, 0, sizeof(float) * (size_t)g.K * Ntot, st);
-  const double xb = 2.0 * ((double)g.N * g.H * g.W * g.xps), db = 2.0 * ((double)NP * g.yps);
-  v3::conv_wgrad_v4<BM, BN><<<grid, 512, 0, st>>>(x, dy, dw, per, g, gm, gn, (unsigned)xb, (unsigned)db);
-  wgrad_end(g, dw, splits, st);
-  return (int)hipGetLastError();
-}
+// ---------------------------------------------------------------- weight-grad
 // tap-fused 3x3 s1 weight-grad (v3::conv_wgrad_tap) where it applies
 inline bool wgrad_tap_ok(const Geom& g, const void* x, const void* dy) {
   if (g.KH != 3 || g.KW != 3 || g.S != 1 || g.P != 1 || g.OH != g.H || g.OW != g.W) return false;
   if (g.C % 16 != 0 || g.xps % 8 != 0 || g.yps % 8 != 0 || g.K % 8 != 0 || !aligned16(x) || !aligned16(dy)) return false;
   // C % 32 == 16 (the space-to-depth stem, 16 channels) included: the upper half of the halo plane loads zeros
   // (yolov5s 3845 -> 3876 img/s against the v3n column tiles, profiles/r05/wgrad_tap16_ab.log)
-  const double xb = 2.0 * ((double)g.N * g.H * g.W * g.xps), db = 2.0 * ((double)g.N * g.OH * g.OW * g.yps);
-  if (xb >= (double)v3::kBufOob || db >= (double)v3::kBufOob) return false;
+  if (!fits_buf(x_bytes(g)) || !fits_buf(y_bytes(g))) return false;
   // enough (patch, tile) work units that the per-block fp32 atomics of the 288-column tile stay a small share
   // (tools/gpu/tune_conv.py: 20^2 / 40^2 / 80^2 yolov5s layers are faster on the v3 / v4 column tiles)
   const long units = (long)g.N * ceil_div(g.OH, 8) * ceil_div(g.OW, 8) * ceil_div(g.K, 128) * ceil_div(g.C, 32);
@@ -4195,113 +4159,133 @@ inline bool wgrad_tap_ok(const Geom& g, const void* x, const void* dy) {
   // (profiles/r05/wgrad_tap_units_ab.log)
   return units >= 10000;
 }
-// the <= 64-output-channel layers with C % 64 == 0 run the two-plane tile (a block owns 64 input channels: 13 fragment
-// reads per 36 MFMAs instead of 11 per 18; DMA-1536 158.4 -> 159.1 img/s, profiles/r05/wgrad_tap_np2_ab.log); the
-// same for the 128-row tile needs 288 accumulators, one block per CU, and measured 2 % slower
-// (profiles/r05/wgrad_tap_np128_ab.log)
-template <int BM, int NP = 1>
-int launch_wgrad_tap(const bf16* x, const bf16* dy, float* dw, Geom g, hipStream_t st) {
-  const int gm = ceil_div(g.K, BM), gn = ceil_div(g.C, 32 * NP);
-  const int nk = g.N * ceil_div(g.OH, 8) * ceil_div(g.OW, 8);  // 8 x 8 patches
-  const int tiles = gm * gn;
-  int maxs = nk / 8;
-  if (maxs < 1) maxs = 1;
-  int splits = 1;
-  {
-    // two resident blocks per CU; ~1.1 us per patch step of the 128-row tile (288 MFMA per wave pair at ~45 %
-    // of peak) and its 147 KiB fp32 tile of atomics per block at 1.3 TB/s (MI355X_MICROARCH.md §Global float
-    // atomics); the 64-row tile halves both
-    const double R = 2.0 * num_cus(), f = BM / 128.0 * NP;
-    double best = 1e300;
-    for (int sp = 1; sp <= maxs; sp += (sp < 16 ? 1 : sp / 16)) {
-      const double blocks = (double)tiles * sp;
-      const double t = ceil(blocks / R) * ceil_div(nk, sp) * 1.1 * f + blocks * 0.113 * f;
-      if (t < best) { best = t; splits = sp; }
-    }
-  }
-  if (splits > maxs) splits = maxs;
-  const int per = ceil_div(nk, splits);
-  splits = ceil_div(nk, per);
-  const dim3 grid((unsigned)tiles, splits);
-  if (wgrad_begin(g, splits)) return 0;
-  if (!g.zeroed) (void)hipMemsetAsync(dw, 0, sizeof(float) * (size_t)g.K * 9 * g.C, st);
-  const double xb = 2.0 * ((double)g.N * g.H * g.W * g.xps), db = 2.0 * ((double)g.N * g.OH * g.OW * g.yps);
-  v3::conv_wgrad_tap<BM, NP><<<grid, 256, 0, st>>>(x, dy, dw, per, g, gm, gn, nk, (unsigned)xb, (unsigned)db);
-  wgrad_end(g, dw, splits, st);
-  return (int)hipGetLastError();
-}
-
-// narrow layers (K <= 64): BM = 32 / 64 out-channel tiles, BN = 128 / 256 column tiles
-template <int BM, int BN>
-int launch_wgrad_v3n(const bf16* x, const bf16* dy, float* dw, Geom g, hipStream_t st) {
-  const long NP = (long)g.N * g.OH * g.OW;
-  const int Ntot = g.KH * g.KW * g.C;
-  const int gm = ceil_div(g.K, BM), gn = ceil_div(Ntot, BN);
-  const int nk = ceil_div(NP, 64);
-  const int tiles = gm * gn;
-  int maxs = nk / 8;
-  if (maxs < 1) maxs = 1;
-  int splits = 1;
-  {
-    // same cost model as launch_wgrad_v3 with the tile's share of a 128 x 128 step and atomics
-    const double R = 2.0 * num_cus() * (128.0 * 128.0) / (BM * BN) * 0.5;
-    const double step = 1.9 * (BM * BN) / (128.0 * 128.0) + 0.25;
-    double best = 1e300;
-    for (int sp = 1; sp <= maxs; sp += (sp < 16 ? 1 : sp / 16)) {
-      const double blocks = (double)tiles * sp;
-      const double t = ceil(blocks / R) * ceil_div(nk, sp) * step + blocks * 0.0504 * (BM * BN) / (128.0 * 128.0);
-      if (t < best) { best = t; splits = sp; }
-    }
-  }
-  if (splits > maxs) splits = maxs;
-  const int per = ceil_div(nk, splits);
-  splits = ceil_div(nk, per);
-  const dim3 grid((unsigned)tiles, splits);
-  if (wgrad_begin(g, splits)) return 0;
-  if (!g.zeroed) (void)hipMemsetAsync(dw, 0, sizeof(float) * (size_t)g.K * Ntot, st);
-  constexpr int NS = 3 * v3::WgradLdsN<BM, BN>::STAGE <= 80 * 1024 ? 3 : 2;  // keep 2 blocks per CU
-  const double xb = 2.0 * ((double)g.N * g.H * g.W * g.xps), db = 2.0 * ((double)NP * g.yps);
-  if (xb < (double)v3::kBufOob && db < (double)v3::kBufOob)
-    v3::conv_wgrad_v3n<BM, BN, NS, true><<<grid, BN, 0, st>>>(x, dy, dw, per, g, gm, gn, (unsigned)xb, (unsigned)db);
-  else
-    v3::conv_wgrad_v3n<BM, BN, NS, false><<<grid, BN, 0, st>>>(x, dy, dw, per, g, gm, gn, 0u, 0u);
-  wgrad_end(g, dw, splits, st);
-  return (int)hipGetLastError();
-}
-
 // weight-grad of layers with <= 64 output channels: 1 = the narrow LDS-DMA tiles (BM 32/64) past 8 M pixels at
 // K = 64, 2 = the 128 x 128 LDS-DMA tile (half its rows idle at K = 64) otherwise (tools/gpu/ab_conv.sh: 64 ch @768^2
 // x 32 narrow 483 / 128-tile 394 / v2 257 TFLOP/s; @384^2 280 / 384 / 261; yolov5s layers 128-tile best)
 inline int wgrad_narrow_for(const Geom& g, long NP) { return (g.K == 64 && NP >= 8L * 1024 * 1024) ? 1 : 2; }
 
+// The weight-grad's plan: the kernel and its split-K (T = the storage type; the LDS-DMA kernels are bf16 only).
+// conv_wgrad_t executes it and dmy_conv_wgrad_ws_elems reads the split count off it.
 template <typename T>
-int conv_wgrad_t(const void* x, const void* dy, float* dw, const Geom& g, hipStream_t st) {
+WPlan plan_wgrad(const Geom& g, const void* x, const void* dy) {
+  const long NP = (long)g.N * g.OH * g.OW;
+  const int Ntot = g.KH * g.KW * g.C;
   if constexpr (sizeof(T) == 2) {
-    const long NP = (long)g.N * g.OH * g.OW;
-    const int Ntot = g.KH * g.KW * g.C;
     const bool vec = g.C % 8 == 0 && g.xps % 8 == 0 && g.K % 8 == 0 && g.yps % 8 == 0 && aligned16(x) && aligned16(dy);
     const int nm = wgrad_narrow_for(g, NP);
-    const double xb4 = 2.0 * ((double)g.N * g.H * g.W * g.xps), db4 = 2.0 * ((double)NP * g.yps);
-    if (wgrad_tap_ok(g, x, dy))
-      return g.K > 64 ? launch_wgrad_tap<128>((const bf16*)x, (const bf16*)dy, dw, g, st)
-             : g.C % 64 == 0 ? launch_wgrad_tap<64, 2>((const bf16*)x, (const bf16*)dy, dw, g, st)
-                             : launch_wgrad_tap<64>((const bf16*)x, (const bf16*)dy, dw, g, st);
-    if (vec && g.K >= 256 && Ntot >= 128 && NP >= 16384 && xb4 < (double)v3::kBufOob && db4 < (double)v3::kBufOob)
-      return launch_wgrad_v4<256, 128>((const bf16*)x, (const bf16*)dy, dw, g, st);
+    const int nk = ceil_div(NP, 64);  // K steps of the column-tile kernels: 64 pixels
+    const double NC = num_cus();
+    if (wgrad_tap_ok(g, x, dy)) {
+      // 128 output rows a tile above 64 output channels.  The <= 64-output-channel layers with C % 64 == 0 run the
+      // two-plane tile (a block owns 64 input channels: 13 fragment reads per 36 MFMAs instead of 11 per 18; DMA-1536
+      // 158.4 -> 159.1 img/s, profiles/r05/wgrad_tap_np2_ab.log); the same for the 128-row tile needs 288 accumulators,
+      // one block per CU, and measured 2 % slower (profiles/r05/wgrad_tap_np128_ab.log)
+      const Kern k = g.K > 64 ? Kern::W_TAP128 : g.C % 64 == 0 ? Kern::W_TAP64X2 : Kern::W_TAP64;
+      const int BM = g.K > 64 ? 128 : 64, planes = k == Kern::W_TAP64X2 ? 2 : 1;
+      const int np = g.N * ceil_div(g.OH, 8) * ceil_div(g.OW, 8);  // K steps: 8 x 8 patches
+      // two resident blocks per CU; ~1.1 us per patch step of the 128-row tile (288 MFMA per wave pair at ~45 % of
+      // peak) and its 147 KiB fp32 tile of atomics per block at 1.3 TB/s (MI355X_MICROARCH.md §Global float atomics);
+      // the 64-row tile halves both
+      const double f = BM / 128.0 * planes;
+      return wgrad_split(k, ceil_div(g.K, BM) * ceil_div(g.C, 32 * planes), np, 2.0 * NC, 1.1 * f, 0.113 * f);
+    }
+    // wgrad v4 tile 256 x 128 for K_out >= 256, else the v3 128 x 128 kernel (tools/gpu/ab_conv.sh,
+    // profiles/r01/ab_wgrad_v4.log: +7-11 % at K_out >= 256, the 256-row tile is half idle and a 128 x 256 one no
+    // faster at K_out = 128).  The v3 model below with one resident block per CU, twice the tile per K step and atomics
+    if (vec && g.K >= 256 && Ntot >= 128 && NP >= 16384 && fits_buf(x_bytes(g)) && fits_buf(y_bytes(g)))
+      return wgrad_split(Kern::W_V4, ceil_div(g.K, 256) * ceil_div(Ntot, 128), nk, NC, 1.9 * 2 * 0.5, 0.0504 * 2);
+    // v3 128 x 128 tile.  Cost model (calibrated on MI355X): resident blocks R = 2 per CU; 1.9 us a K step; 64 KiB of
+    // fp32 atomics a block at 1.3 TB/s.  It beat fixed 512 / 768-block targets on DMA-1536 (152.15 vs 150.76 / 147.91
+    // img/s, profiles/r04/wgrad_target_ab.log)
     if (vec && (g.K > 64 || nm == 2) && Ntot >= 64 && NP >= 16384)
-      return launch_wgrad_v3((const bf16*)x, (const bf16*)dy, dw, g, st);
+      return wgrad_split(Kern::W_V3, ceil_div(g.K, 128) * ceil_div(Ntot, 128), nk, 2.0 * NC, 1.9, 0.0504);
     if (vec && g.K <= 64 && Ntot >= 128 && NP >= 16384 && nm == 1) {
-      // one 256-column tile also for 128 < Ntot < 256 (the 144-column space-to-depth stem view: on 128-column tiles
-      // the second tile re-read every dy row for 16 columns of work; profiles/r04/stem_wgrad_ab.log 1638 -> 1276 us)
+      // narrow layers: BM = 32 / 64 out-channel tiles, BN = 128 / 256 column tiles.  One 256-column tile also for
+      // 128 < Ntot < 256 (the 144-column space-to-depth stem view: on 128-column tiles the second tile re-read every
+      // dy row for 16 columns of work; profiles/r04/stem_wgrad_ab.log 1638 -> 1276 us)
       const bool wide = Ntot >= 512 || Ntot % 256 == 0 || (Ntot > 128 && Ntot < 256);
-      if (g.K <= 32) return wide ? launch_wgrad_v3n<32, 256>((const bf16*)x, (const bf16*)dy, dw, g, st)
-                                 : launch_wgrad_v3n<32, 128>((const bf16*)x, (const bf16*)dy, dw, g, st);
-      return wide ? launch_wgrad_v3n<64, 256>((const bf16*)x, (const bf16*)dy, dw, g, st)
-                  : launch_wgrad_v3n<64, 128>((const bf16*)x, (const bf16*)dy, dw, g, st);
+      const int BM = g.K <= 32 ? 32 : 64, BN = wide ? 256 : 128;
+      // the v3 model with the tile's share of a 128 x 128 step and atomics
+      const double R = 2.0 * NC * (128.0 * 128.0) / (BM * BN) * 0.5;
+      const double step = 1.9 * (BM * BN) / (128.0 * 128.0) + 0.25;
+      return wgrad_split(wide ? Kern::W_V3N256 : Kern::W_V3N128, ceil_div(g.K, BM) * ceil_div(Ntot, BN), nk, R, step,
+                         0.0504 * (BM * BN) / (128.0 * 128.0));
     }
   }
-  if (g.K > 64 && g.KH * g.KW * g.C > 64) return launch_wgrad<T, 128, 128>((const T*)x, (const T*)dy, dw, g, st);
-  return launch_wgrad<T, 64, 64>((const T*)x, (const T*)dy, dw, g, st);
+  const int nk = ceil_div(NP, Cfg<T>::BK);
+  if (g.K > 64 && Ntot > 64) return wgrad_split_v2(Kern::W_V2_128, ceil_div(g.K, 128) * ceil_div(Ntot, 128), nk);
+  return wgrad_split_v2(Kern::W_V2_64, ceil_div(g.K, 64) * ceil_div(Ntot, 64), nk);
+}
+
+inline void launch_wgrad_v3(const bf16* x, const bf16* dy, float* dw, const Geom& g, hipStream_t st, const WPlan& pl) {
+  const int Ntot = g.KH * g.KW * g.C;
+  const int gm = ceil_div(g.K, 128), gn = ceil_div(Ntot, 128);
+  const dim3 grid((unsigned)gm * gn, pl.splits);
+  const double xb = x_bytes(g), db = y_bytes(g);
+  if (fits_buf(xb) && fits_buf(db))
+    v3::conv_wgrad_v3<2, 1><<<grid, 256, 0, st>>>(x, dy, dw, pl.per, g, gm, gn, (unsigned)xb, (unsigned)db);
+  else
+    v3::conv_wgrad_v3<2, 0><<<grid, 256, 0, st>>>(x, dy, dw, pl.per, g, gm, gn, 0u, 0u);
+}
+
+inline void launch_wgrad_v4(const bf16* x, const bf16* dy, float* dw, const Geom& g, hipStream_t st, const WPlan& pl) {
+  const int Ntot = g.KH * g.KW * g.C;
+  const int gm = ceil_div(g.K, 256), gn = ceil_div(Ntot, 128);
+  const dim3 grid((unsigned)gm * gn, pl.splits);
+  v3::conv_wgrad_v4<256, 128><<<grid, 512, 0, st>>>(x, dy, dw, pl.per, g, gm, gn, (unsigned)x_bytes(g),
+                                                    (unsigned)y_bytes(g));
+}
+
+template <int BM, int NP = 1>
+void launch_wgrad_tap(const bf16* x, const bf16* dy, float* dw, const Geom& g, hipStream_t st, const WPlan& pl) {
+  const int gm = ceil_div(g.K, BM), gn = ceil_div(g.C, 32 * NP);
+  const int nk = g.N * ceil_div(g.OH, 8) * ceil_div(g.OW, 8);  // 8 x 8 patches
+  const dim3 grid((unsigned)gm * gn, pl.splits);
+  v3::conv_wgrad_tap<BM, NP><<<grid, 256, 0, st>>>(x, dy, dw, pl.per, g, gm, gn, nk, (unsigned)x_bytes(g),
+                                                   (unsigned)y_bytes(g));
+}
+
+template <int BM, int BN>
+void launch_wgrad_v3n(const bf16* x, const bf16* dy, float* dw, const Geom& g, hipStream_t st, const WPlan& pl) {
+  const int Ntot = g.KH * g.KW * g.C;
+  const int gm = ceil_div(g.K, BM), gn = ceil_div(Ntot, BN);
+  const dim3 grid((unsigned)gm * gn, pl.splits);
+  constexpr int NS = 3 * v3::WgradLdsN<BM, BN>::STAGE <= 80 * 1024 ? 3 : 2;  // keep 2 blocks per CU
+  const double xb = x_bytes(g), db = y_bytes(g);
+  if (fits_buf(xb) && fits_buf(db))
+    v3::conv_wgrad_v3n<BM, BN, NS, true><<<grid, BN, 0, st>>>(x, dy, dw, pl.per, g, gm, gn, (unsigned)xb, (unsigned)db);
+  else
+    v3::conv_wgrad_v3n<BM, BN, NS, false><<<grid, BN, 0, st>>>(x, dy, dw, pl.per, g, gm, gn, 0u, 0u);
+}
+
+template <typename T>
+int conv_wgrad_t(const void* x, const void* dy, float* dw, Geom g, hipStream_t st) {
+  const WPlan pl = plan_wgrad<T>(g, x, dy);
+  // deterministic mode with one split keeps the single atomic per element (exact: it adds to a zero or to an earlier
+  // stream-ordered launch's value), so the workspace is dropped
+  if (pl.splits <= 1) g.dws = nullptr;
+  if (!g.zeroed) (void)hipMemsetAsync(dw, 0, sizeof(float) * (size_t)g.K * g.KH * g.KW * g.C, st);
+  const bf16 *a = (const bf16*)x, *b = (const bf16*)dy;
+  const bool k32 = g.K <= 32;
+  switch (sizeof(T) == 2 ? pl.k : Kern::V2) {
+    case Kern::W_TAP128: launch_wgrad_tap<128>(a, b, dw, g, st, pl); break;
+    case Kern::W_TAP64X2: launch_wgrad_tap<64, 2>(a, b, dw, g, st, pl); break;
+    case Kern::W_TAP64: launch_wgrad_tap<64>(a, b, dw, g, st, pl); break;
+    case Kern::W_V4: launch_wgrad_v4(a, b, dw, g, st, pl); break;
+    case Kern::W_V3: launch_wgrad_v3(a, b, dw, g, st, pl); break;
+    case Kern::W_V3N256:
+      k32 ? launch_wgrad_v3n<32, 256>(a, b, dw, g, st, pl) : launch_wgrad_v3n<64, 256>(a, b, dw, g, st, pl);
+      break;
+    case Kern::W_V3N128:
+      k32 ? launch_wgrad_v3n<32, 128>(a, b, dw, g, st, pl) : launch_wgrad_v3n<64, 128>(a, b, dw, g, st, pl);
+      break;
+    default:
+      if (pl.k == Kern::W_V2_128) launch_wgrad<T, 128, 128>((const T*)x, (const T*)dy, dw, g, st, pl);
+      else launch_wgrad<T, 64, 64>((const T*)x, (const T*)dy, dw, g, st, pl);
+  }
+  if (g.dws != nullptr)  // deterministic mode: sum the splits' workspace slabs into dw, in split order
+    wgrad_split_reduce<<<grid_cap(ceil_div(g.dws_slab, 256), 2048), 256, 0, st>>>(g.dws, dw, g.dws_slab, pl.splits);
+  return (int)hipGetLastError();
 }
 
 }  // namespace
@@ -4539,13 +4523,28 @@ DMY_API int dmy_conv_wgrad_ex(int dtype, const void* x, const void* dy, float* d
 // deterministic weight-grad: fp32 workspace elements it needs (0 = the dispatch uses one split: no workspace)
 DMY_API long dmy_conv_wgrad_ws_elems(int dtype, const void* x, const void* dy, int N, int H, int W, int C, long xps,
                                      int K, int KH, int KW, int S, int P, int OH, int OW, long yps, int flags) {
-  Geom g = make_geom(N, H, W, C, xps, K, KH, KW, S, P, OH, OW, yps);
-  g.oihw = flags & DMY_WGRAD_OIHW ? 1 : 0;
-  g.zeroed = flags & DMY_WGRAD_ZEROED ? 1 : 0;
-  int splits = 1;
-  g.plan = &splits;
-  (void)(dtype ? conv_wgrad_t<bf16>(x, dy, nullptr, g, nullptr) : conv_wgrad_t<float>(x, dy, nullptr, g, nullptr));
+  (void)flags;  // the output layout and the memset do not change the split
+  const Geom g = make_geom(N, H, W, C, xps, K, KH, KW, S, P, OH, OW, yps);
+  const int splits = dtype ? plan_wgrad<bf16>(g, x, dy).splits : plan_wgrad<float>(g, x, dy).splits;
   return splits > 1 ? (long)splits * K * KH * KW * C : 0;
+}
+
+// The kernel (DMY_KERN_*) the dispatch takes for these arguments; the pointers are only tested for alignment.
+DMY_API int dmy_conv_route(int pass, int dtype, const void* a, const void* b, const void* c, int N, int H, int W, int C,
+                           long xps, int K, int KH, int KW, int S, int P, int OH, int OW, long yps, int acc) {
+  static_assert((int)Kern::V2 == DMY_KERN_V2 && (int)Kern::S2_CLASS == DMY_KERN_S2_CLASS &&
+                    (int)Kern::W_V4 == DMY_KERN_W_V4 && (int)Kern::W_V2_64 == DMY_KERN_W_V2_64,
+                "Kern and the header's DMY_KERN_* codes number alike");
+  const Geom g = make_geom(N, H, W, C, xps, K, KH, KW, S, P, OH, OW, yps);
+  switch (pass) {
+    case 0:  // training forward without bias: a = x, b = w_ohwi, c = y
+      return (int)(dtype ? plan_fwd(g, a, b, nullptr, c, true, Epi{}, 0).k : Kern::V2);
+    case 1:  // data-grad: a = dy, b = w_ihwo, c = dx
+      return S > 2 ? -1 : (int)(dtype ? plan_dgrad(g, a, b, c, acc) : plan_dgrad_v2(g)).k;
+    case 2:  // weight-grad: a = x, b = dy
+      return (int)(dtype ? plan_wgrad<bf16>(g, a, b) : plan_wgrad<float>(g, a, b)).k;
+    default: return -1;
+  }
 }
 
 DMY_API int dmy_conv_wgrad_det(int dtype, const void* x, const void* dy, float* dw, int N, int H, int W, int C,

@@ -18,7 +18,8 @@ P, I, L, F, D = ctypes.c_void_p, ctypes.c_int, ctypes.c_long, ctypes.c_float, ct
 
 # name -> argtypes, exactly the header's parameter list (tests/test_abi.py derives both from include/dmayolo.h and
 # compares them); the return type is the header's: long for the *_bytes / *_elems queries and the *_bound_rows /
-# *_last_rows queries, else int (a hipError_t, or a size for the *_rows / *_blocks / *_groups queries)
+# *_last_rows queries, else int (a hipError_t, a size for the *_rows / *_blocks / *_groups queries, or a KERN code
+# for dmy_conv_route)
 SIGNATURES = {
     # conv.hip
     'dmy_conv_fwd_partial_rows': [L, I],
@@ -38,6 +39,7 @@ SIGNATURES = {
     'dmy_conv_wgrad_ex': [I, P, P, P, I, I, I, I, L, I, I, I, I, I, I, I, L, I, P],
     'dmy_conv_wgrad_ws_elems': [I, P, P, I, I, I, I, L, I, I, I, I, I, I, I, L, I],
     'dmy_conv_wgrad_det': [I, P, P, P, I, I, I, I, L, I, I, I, I, I, I, I, L, I, P, L, P],
+    'dmy_conv_route': [I, I, P, P, P, I, I, I, I, L, I, I, I, I, I, I, I, L, I],
     'dmy_conv_wprep': [I, P, P, P, I, I, I, I, I, P],
     # bwd1x1.hip
     'dmy_conv1x1_bwd_bn_ok': [L, I, I, L, L, L, P, P, P, P],
@@ -152,6 +154,13 @@ SIGNATURES = {
 }
 
 
+# dmy_conv_route's return value: the DMY_KERN_* codes of include/dmayolo.h, in order
+KERN = {n: i for i, n in enumerate(
+    ['HALO', 'SPLITK', 'P1S', 'STEM', 'P1P', 'PIPE8', 'WIDE', 'WIDE288', 'TALL', 'V3', 'V2',
+     'V2_BIG', 'S2_Q2S', 'S2_Q2', 'S2_MERGED', 'S2_CLASS',
+     'W_TAP128', 'W_TAP64', 'W_TAP64X2', 'W_V4', 'W_V3', 'W_V3N128', 'W_V3N256', 'W_V2_128', 'W_V2_64'])}
+ROUTE_FWD, ROUTE_DGRAD, ROUTE_WGRAD = 0, 1, 2
+
 # symbols whose argtypes dmayolo/optim.py sets itself (multi-tensor optimizer / GradScaler / EMA kernels)
 SELF_BOUND = {'dmy_chunk_size', 'dmy_sgd', 'dmy_adam', 'dmy_ema', 'dmy_amp_check', 'dmy_amp_update'}
 LONG_RET = {'dmy_conv_fwd_bound_rows', 'dmy_conv_fwd_last_rows'}
@@ -182,7 +191,7 @@ lib = _load()
 
 def call(name, *args):
     rc = getattr(lib, name)(*args)
-    if name.endswith(('_rows', '_blocks', '_groups', '_bytes', '_elems', '_ok')):
+    if name.endswith(('_rows', '_blocks', '_groups', '_bytes', '_elems', '_ok', '_route')):
         return rc
     if rc != 0:
         raise RuntimeError(f'{name} failed with hipError {rc}')

@@ -84,6 +84,44 @@ long dmy_conv_wgrad_ws_elems(int dtype, const void* x, const void* dy, int N, in
 int dmy_conv_wgrad_det(int dtype, const void* x, const void* dy, float* dw, int N, int H, int W, int C, long xps,
                        int K, int KH, int KW, int S, int P, int OH, int OW, long yps, int flags, float* ws,
                        long ws_elems, void* stream);
+/* Route query: the kernel the dispatch takes for these arguments, from the plan the launch itself executes (csrc/conv.hip
+ * plan_fwd / plan_dgrad / plan_wgrad).  Launches nothing and never dereferences a, b, c (only their 16-byte alignment
+ * counts).  pass 0 = training forward without bias (a = x, b = w_ohwi, c = y), 1 = data-grad (a = dy, b = w_ihwo,
+ * c = dx; acc = accumulate), 2 = weight-grad (a = x, b = dy, c unused).  Returns a DMY_KERN_* code, or -1 for an
+ * unknown pass or a stride the data-grad does not support.  Several rules count blocks per CU, so the route of a
+ * shape depends on the device's CU count. */
+int dmy_conv_route(int pass, int dtype, const void* a, const void* b, const void* c, int N, int H, int W, int C,
+                   long xps, int K, int KH, int KW, int S, int P, int OH, int OW, long yps, int acc);
+enum {
+  /* forward, and stride-1 data-grads (a forward over dy) */
+  DMY_KERN_HALO = 0,     /* persistent 3x3 64 -> 64 halo kernel (conv3_halo64) */
+  DMY_KERN_SPLITK = 1,   /* small-M split-K forward (conv_fwd_split + splitk_epi; dmy_conv_fwd_act_ws only) */
+  DMY_KERN_P1S = 2,      /* 1x1 streaming GEMM (conv_p1s) */
+  DMY_KERN_STEM = 3,     /* 16-channel 3x3 stem view on the streaming GEMM's gather */
+  DMY_KERN_P1P = 4,      /* persistent 1x1 GEMM with the register epilogue (conv_p1p) */
+  DMY_KERN_PIPE8 = 5,    /* 1x1 256 x 256 half-tile pipeline (conv_fwd_8p) */
+  DMY_KERN_WIDE = 6,     /* 256 x 256 wide tile (conv_fwd_w) */
+  DMY_KERN_WIDE288 = 7,  /* 288 x 256 wide tile */
+  DMY_KERN_TALL = 8,     /* 512 x 128 tall tile */
+  DMY_KERN_V3 = 9,       /* LDS-DMA 256 x 128 / 256 x 64 tiles (conv_fwd_v3) */
+  DMY_KERN_V2 = 10,      /* register-staged tiles (forward: either size; data-grad: 64 x 64) */
+  /* data-grad only */
+  DMY_KERN_V2_BIG = 11,     /* register-staged 128 x 128 tile */
+  DMY_KERN_S2_Q2S = 12,     /* stride 2 as one GEMM over dy pixels, 32 channels (conv_dgrad_q2s) */
+  DMY_KERN_S2_Q2 = 13,      /* the same for 64 / 128 channels (conv_dgrad_q2) */
+  DMY_KERN_S2_MERGED = 14,  /* stride 2, the four parity classes in one launch (conv_dgrad_s2_v3) */
+  DMY_KERN_S2_CLASS = 15,   /* stride 2, one launch a class: 256 / 288 x 256 wide tile or 256 x 128 */
+  /* weight-grad */
+  DMY_KERN_W_TAP128 = 16,   /* tap-fused 3x3, 128-row tile (conv_wgrad_tap) */
+  DMY_KERN_W_TAP64 = 17,    /* tap-fused, 64-row tile */
+  DMY_KERN_W_TAP64X2 = 18,  /* tap-fused, 64-row tile over two halo planes */
+  DMY_KERN_W_V4 = 19,       /* 256 x 128 tile (conv_wgrad_v4) */
+  DMY_KERN_W_V3 = 20,       /* 128 x 128 tile (conv_wgrad_v3) */
+  DMY_KERN_W_V3N128 = 21,   /* narrow tile, 32 / 64 rows x 128 columns (conv_wgrad_v3n) */
+  DMY_KERN_W_V3N256 = 22,   /* narrow tile, 32 / 64 rows x 256 columns */
+  DMY_KERN_W_V2_128 = 23,   /* register-staged 128 x 128 tile */
+  DMY_KERN_W_V2_64 = 24     /* register-staged 64 x 64 tile */
+};
 /* Cp >= C: input channels zero-padded to a full 16-byte vector (the 3-channel stem, yaml:15) */
 int dmy_conv_wprep(int dtype, const float* w_oihw, void* w_ohwi, void* w_ihwo, int K, int C, int Cp, int KH, int KW,
                    void* stream);

@@ -12,19 +12,26 @@ SHAPES = [(2, 16, 20, 18, 24, 3, 1), (4, 64, 40, 40, 64, 3, 2), (8, 64, 40, 40, 
           (16, 128, 40, 40, 256, 1, 1), (16, 64, 64, 64, 128, 3, 2), (12, 96, 37, 45, 136, 3, 1),
           (9, 256, 48, 50, 384, 1, 1), (8, 8, 192, 192, 64, 6, 2), (8, 8, 192, 192, 128, 6, 2),
           (4, 40, 96, 70, 200, 3, 1),
-          # narrow layers (K <= 64) on the LDS-DMA weight-grad tiles (BM 32/64 x BN 128/256), ragged K / columns
+          # narrow layers (K <= 64), ragged K / columns: their weight-grads run the 128 x 128 LDS-DMA tile (the narrow
+          # BM 32/64 x BN 128/256 tiles start at 8 M pixels, too large for this suite; test_conv_routes pins that rule)
           (16, 32, 64, 64, 32, 3, 1), (4, 64, 80, 80, 64, 3, 1), (16, 256, 40, 40, 64, 1, 1),
           (8, 8, 192, 192, 32, 6, 2), (8, 136, 60, 50, 40, 1, 1), (8, 32, 96, 96, 64, 3, 2),
           # buffer-descriptor v3 loader (C % 64 == 0): ragged M and K, 3 K steps per tap, stride 2
           (11, 128, 37, 45, 200, 3, 1), (6, 192, 52, 60, 136, 3, 1), (4, 64, 130, 122, 256, 3, 2),
           # stride-2 data-grad on the buffer loader, one launch per parity class: odd sizes, 3 K steps per tap
           (12, 64, 75, 91, 128, 3, 2), (8, 128, 101, 99, 192, 3, 2),
-          # wide 256 x 256 tiles (>= 256 GEMM columns, >= one block per CU): fwd + dgrad, and dgrad of a 1x1
+          # wide 256 x 256 tiles (>= 256 GEMM columns, >= one block per CU): fwd + dgrad of the first, fwd with ragged
+          # M and columns of the third; the 1x1's data-grad (512 <- 128) runs the streaming GEMM
           (16, 256, 64, 64, 256, 3, 1), (16, 512, 64, 64, 128, 1, 1), (17, 256, 61, 63, 264, 3, 1),
-          # 512 x 128 tiles (65..128 GEMM columns, >= one block per CU), ragged M and columns
+          # 65..128 GEMM columns below the tall tile's 4 blocks per CU: 256 x 128 LDS-DMA tiles (3x3), the persistent
+          # 1x1 GEMM with ragged M and columns
           (32, 128, 64, 64, 128, 3, 1), (33, 128, 65, 63, 104, 1, 1),
-          # 1x1 streaming GEMM (conv_p1s, reduction 64 / 128 / 256): odd 64-row tile counts (zeroed pad partial row),
-          # 32-column passes, the per-32-row partials of <= 64-column layers, several column groups
+          # 512 x 128 tall tile (k > 1, 65..128 GEMM columns, >= 4 blocks per CU: 1024 row tiles on 256 CUs), ragged M
+          # and columns
+          (33, 128, 127, 125, 104, 3, 1),
+          # 1x1 layers with reduction 64 / 96 / 128 / 256, odd 64-row tile counts, 32-column tails: the streaming GEMM
+          # (conv_p1s, >= 2x as many columns as reduction: the last two forwards) with its zeroed pad partial row, the
+          # persistent 1x1 GEMM and the 256-row LDS-DMA tiles for the rest
           (5, 128, 57, 63, 96, 1, 1), (6, 64, 55, 57, 64, 1, 1), (4, 256, 65, 67, 288, 1, 1), (5, 96, 57, 63, 128, 1, 1),
           (3, 64, 97, 89, 544, 1, 1), (5, 128, 57, 63, 288, 1, 1),
           # the 16-channel k3 view of the space-to-depth stem on the streaming GEMM's 3x3 gather (zero taps at the
@@ -102,6 +109,7 @@ def test_conv_dgrad_s2_one_gemm_vs_torch(N, H, W, K, acc, C):
     even and odd maps (the a = 1 / b = 1 rows and columns past an odd edge are not stored), 64 / 128 / 192 dy channels,
     accumulate."""
     from dmayolo.functional import call, ptr, stream, prep_weight
+    from dmayolo._lib import KERN, ROUTE_DGRAD
     k, s, p = 3, 2, 1
     g = torch.Generator().manual_seed(N * 1000 + H + K)
     w = (torch.randn(K, C, k, k, generator=g) / (K * k * k) ** 0.5)
@@ -114,6 +122,9 @@ def test_conv_dgrad_s2_one_gemm_vs_torch(N, H, W, K, acc, C):
     _, wt = prep_weight(w.cuda(), torch.bfloat16, True)
     dyd = dy.cuda().contiguous(memory_format=torch.channels_last)
     dx = prev.cuda().contiguous(memory_format=torch.channels_last)
+    # the one-GEMM kernel is what runs (>= one 256-row tile per CU: the smallest shape has exactly 256 tiles)
+    route = call('dmy_conv_route', ROUTE_DGRAD, 1, ptr(dyd), ptr(wt), ptr(dx), N, H, W, C, C, K, k, k, s, p, OH, OW, K, acc)
+    assert route == KERN['S2_Q2S' if C == 32 else 'S2_Q2'], route
     rc = call('dmy_conv_dgrad', 1, ptr(dyd), ptr(wt), ptr(dx), acc, N, H, W, C, C, K, k, k, s, p, OH, OW, K, stream())
     assert rc == 0
     torch.cuda.synchronize()
@@ -144,6 +155,93 @@ def test_conv_wgrad_bf16_vs_torch(N, C, H, W, K, k, s):
     call('dmy_conv_wgrad_to_oihw', ptr(dwo), ptr(dw), K, C, C, k, k, stream())
     torch.cuda.synchronize()
     assert _rel(dw, ref) < 2e-3
+
+
+def _cd(a, b):
+    return -(-a // b)
+
+
+def _wide(M, gn, NC):
+    """the wide tile of M rows x gn 256-column tiles: 288 rows when that grid ends in fewer row-weighted rounds"""
+    return 'WIDE288' if _cd(_cd(M, 288) * gn, NC) * 288 < _cd(_cd(M, 256) * gn, NC) * 256 else 'WIDE'
+
+
+def test_conv_routes():
+    """dmy_conv_route (query only, no launch): one shape per data-grad and weight-grad kernel kind, the expected kind
+    worked out by hand from the routing rules of csrc/conv.hip (plan_dgrad / plan_v3 / plan_wgrad) with the device's
+    CU count NC; on 256 CUs every kind is reached.  Shapes are (N, C, H, W, K, k, s) from SHAPES, the tap list and the
+    bench-shape lists where those reach the kind."""
+    from dmayolo._lib import call, KERN, ROUTE_DGRAD, ROUTE_WGRAD
+    NC = torch.cuda.get_device_properties(0).multi_processor_count
+    A, B, C_ = 1 << 30, 2 << 30, 3 << 30  # 16-byte aligned addresses; the query never reads them
+
+    def route(ps, shape, off=0, acc=0):
+        N, C, H, W, K, k, s = shape
+        p = k // 2 if k != 6 else 2
+        OH, OW = (H + 2 * p - k) // s + 1, (W + 2 * p - k) // s + 1
+        return call('dmy_conv_route', ps, 1, A + off, B, C_, N, H, W, C, C, K, k, k, s, p, OH, OW, K, acc)
+
+    dgrad = [
+        # M = 720 rows: under the LDS-DMA kernels' 16384 and the 128-row tile's 4096
+        ((2, 16, 20, 18, 24, 3, 1), 0, 0, 'V2'),
+        # M = 4608 < 16384; 36 x 8 = 288 >= 256 tiles of 128 x 128
+        ((2, 1024, 48, 48, 1024, 3, 1), 0, 0, 'V2_BIG'),
+        # stride 2, 3x3, K % 64 == 0, 32 / 64 channels: one GEMM with >= NC 256-row tiles of dy pixels (6400, 1600,
+        # 64), else the four classes merged
+        ((64, 32, 320, 320, 64, 3, 2), 0, 0, 'S2_Q2S' if 6400 >= NC else 'S2_MERGED'),
+        ((64, 64, 160, 160, 128, 3, 2), 0, 0, 'S2_Q2' if 1600 >= NC else 'S2_MERGED'),
+        ((16, 64, 64, 64, 128, 3, 2), 0, 0, 'S2_Q2' if 64 >= NC else 'S2_MERGED'),
+        # 256 channels: no one-GEMM form, one launch a class
+        ((32, 256, 192, 192, 512, 3, 2), 0, 0, 'S2_CLASS'),
+        # 3x3 64 <- 64, 32 x 48 x 12 = 18432 halo tiles >= NC
+        ((32, 64, 384, 384, 64, 3, 1), 0, 0, 'HALO' if 18432 >= NC else 'V3'),
+        # 1x1 512 <- 128: >= 2x the dy channels, one column group
+        ((32, 512, 192, 192, 128, 1, 1), 0, 0, 'P1S'),
+        # 1x1 128 <- 128: persistent GEMM; not when accumulating (then 256 x 128 tiles: 128 columns, 1x1 is not tall)
+        ((32, 128, 192, 192, 128, 1, 1), 0, 0, 'P1P'),
+        ((32, 128, 192, 192, 128, 1, 1), 0, 1, 'V3'),
+        # 1x1 512 <- 512: > 256 columns, 288 x 2 = 576 wide tiles >= NC
+        ((32, 512, 48, 48, 512, 1, 1), 0, 0, 'PIPE8' if 576 >= NC else 'V3'),
+        # 3x3 256 <- 256: 256 (one round of 256 CUs) and 1152 (4.5 rounds) wide tiles
+        ((16, 256, 64, 64, 256, 3, 1), 0, 0, _wide(65536, 1, NC) if 256 >= NC else 'V3'),
+        ((32, 256, 96, 96, 256, 3, 1), 0, 0, _wide(294912, 1, NC) if 1152 >= NC else 'V3'),
+        # 3x3 128 <- 128: 2304 tall tiles >= 4 NC; 256 of them are not
+        ((32, 128, 192, 192, 128, 3, 1), 0, 0, 'TALL' if 2304 >= 4 * NC else 'V3'),
+        ((32, 128, 64, 64, 128, 3, 1), 0, 0, 'TALL' if 256 >= 4 * NC else 'V3'),
+        # 96 dy channels (not a multiple of 64: no buffer loader, so no wide / tall tile)
+        ((12, 96, 37, 45, 136, 3, 1), 0, 0, 'V3'),
+        # dy two bytes off 16-byte alignment: register-staged, 1024 tiles of 128 x 128
+        ((32, 128, 64, 64, 128, 3, 1), 2, 0, 'V2_BIG'),
+    ]
+    wgrad = [
+        # 3x3 s1 with >= 10000 (patch, tile) units: tap-fused; 128 rows above 64 output channels, else 64 rows, over two
+        # planes when C % 64 == 0
+        ((16, 128, 100, 104, 128, 3, 1), 0, 'W_TAP128'),
+        ((8, 16, 288, 288, 64, 3, 1), 0, 'W_TAP64'),
+        ((16, 64, 160, 160, 64, 3, 1), 0, 'W_TAP64X2'),
+        # 1x1, >= 256 output channels, 128 columns, 25600 pixels
+        ((16, 128, 40, 40, 256, 1, 1), 0, 'W_V4'),
+        # stride 2 (no tap kernel), 128 output channels
+        ((16, 64, 64, 64, 128, 3, 2), 0, 'W_V3'),
+        # 64 output channels past 8 M pixels (9.4 M), 1x1: 128-column tiles for 128 columns, one 256-column tile for 256
+        ((64, 128, 384, 384, 64, 1, 1), 0, 'W_V3N128'),
+        ((64, 256, 384, 384, 64, 1, 1), 0, 'W_V3N256'),
+        # under 16384 pixels
+        ((8, 64, 40, 40, 128, 3, 1), 0, 'W_V2_128'),
+        ((2, 16, 20, 18, 24, 3, 1), 0, 'W_V2_64'),
+        # x two bytes off 16-byte alignment
+        ((16, 64, 64, 64, 128, 3, 2), 2, 'W_V2_128'),
+    ]
+    got = [(sh, off, acc, want, route(ROUTE_DGRAD, sh, off, acc)) for sh, off, acc, want in dgrad]
+    bad = [g for g in got if g[4] != KERN[g[3]]]
+    assert not bad, bad
+    gotw = [(sh, off, want, route(ROUTE_WGRAD, sh, off)) for sh, off, want in wgrad]
+    badw = [g for g in gotw if g[3] != KERN[g[2]]]
+    assert not badw, badw
+    if NC == 256:  # every kind has its shape
+        assert {w for _, _, _, w in dgrad} == {'V2', 'V2_BIG', 'S2_Q2S', 'S2_Q2', 'S2_MERGED', 'S2_CLASS', 'HALO', 'P1S',
+                                              'P1P', 'PIPE8', 'WIDE', 'WIDE288', 'TALL', 'V3'}
+        assert {w for _, _, w in wgrad} == {k for k in KERN if k.startswith('W_')}
 
 
 # small-M forward (batch-1 inference) on the split-K path: (N, C, H, W, K, k, s); 1x1 layers stay unsplit by default
