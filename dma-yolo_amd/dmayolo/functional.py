@@ -7,6 +7,7 @@ hot path (torch is used for allocation and the current stream only).
 """
 import os
 import weakref
+from collections import namedtuple
 
 import torch
 
@@ -61,18 +62,14 @@ def const_vec(n, value, dev):
     return t
 
 
-# Output-into-slice side channel of conv_bn_act (see concat_buffer): the view is consumed by the ConvBNActFn.apply
-# that conv_bn_act issues right after setting it, and only when its shape / dtype / device match the output.
-_OUT = [None]
-
-
-def _take_out(N, K, OH, OW, like):
-    o, _OUT[0] = _OUT[0], None
-    if o is None or tuple(o.shape) != (N, K, OH, OW) or o.dtype != like.dtype or o.device != like.device:
-        return None
-    if pixel_stride(o)[0] is not o:  # not NHWC-addressable in place (pixel_stride would copy): a fresh output instead
-        return None
-    return o
+def out_view(o, shape, like):
+    """The output-into-slice rule (see concat_buffer): -> (o, its pixel stride) when the view `o` can take a result of
+    `shape` in place of a fresh tensor like `like` -- same shape, dtype and device, NHWC-addressable in place -- else
+    (None, None).  The Functions take the view as None or [view], so autograd does not see the buffer as an input."""
+    if o is None or tuple(o.shape) != tuple(shape) or o.dtype != like.dtype or o.device != like.device:
+        return None, None
+    t, ps = pixel_stride(o)  # a view that is not addressable in place comes back as a copy: a fresh output instead
+    return (o, ps) if t is o else (None, None)
 
 
 def concat_buffer(N, Ct, H, W, like):
@@ -165,16 +162,36 @@ def set_deterministic(on=True):
     DETERMINISTIC[0] = bool(on)
 
 
-def _wgrad(dt, x, dz, dw, N, H, W, C, xps, K, k, s, p, OH, OW, dzps, flags, fl, **kw):
-    """one weight-gradient launch (atomic split-K, or the deterministic workspace form)"""
+class ConvGeom(namedtuple('ConvGeom', 'N C H W xps K k s p OH OW M Cg Hg Wg kg sg pg Cp s2d')):
+    """Geometry of one conv layer call, built once in ConvBNActFn.forward.  N C H W xps K k s p OH OW (M = N * OH * OW
+    output pixels) describe the layer as the model sees it (timer flops and tags, gradient shapes); Cg Hg Wg kg sg pg
+    are what the kernels are launched with.  The two differ only for the stem forms: space-to-depth (s2d = Cs, the k6
+    s2 p2 conv runs as k3 s1 p1 over Cs channels of the half-size image) and channel-padded (Cp = Cg > C, the
+    zero-padded storage read as 16-byte vectors against zero weights).  Otherwise s2d = 0 and Cp = C."""
+    __slots__ = ()
+
+    def launch(self):  # the geometry arguments shared by the forward / weight-grad kernels, up to the output size
+        return self.N, self.Hg, self.Wg, self.Cg, self.xps, self.K, self.kg, self.kg, self.sg, self.pg, self.OH, self.OW
+
+    def tag(self):
+        return self.N, self.C, self.H, self.W, self.K, self.k, self.s
+
+    def flops(self):
+        return 2.0 * self.M * self.K * self.C * self.k * self.k
+
+
+def _wgrad(dt, x, dz, dzps, dw, g, flags):
+    """one weight-gradient launch over the launch geometry (atomic split-K, or the deterministic workspace form)"""
+    kw = dict(tag=g.tag(), nbytes=x.element_size() * (g.N * g.Hg * g.Wg * g.Cg + g.M * g.K) +
+              4 * g.K * g.Cg * g.kg * g.kg)
     if DETERMINISTIC[0]:
-        ne = call('dmy_conv_wgrad_ws_elems', dt, ptr(x), ptr(dz), N, H, W, C, xps, K, k, k, s, p, OH, OW, dzps, flags)
+        ne = call('dmy_conv_wgrad_ws_elems', dt, ptr(x), ptr(dz), *g.launch(), dzps, flags)
         ws = f32(ne, dz.device) if ne else None
-        KernelTimer.run('conv_wgrad', fl, 'dmy_conv_wgrad_det', dt, ptr(x), ptr(dz), ptr(dw), N, H, W, C, xps, K, k, k,
-                        s, p, OH, OW, dzps, flags, ptr(ws), ne, stream(), **kw)
+        KernelTimer.run('conv_wgrad', g.flops(), 'dmy_conv_wgrad_det', dt, ptr(x), ptr(dz), ptr(dw), *g.launch(), dzps,
+                        flags, ptr(ws), ne, stream(), **kw)
     else:
-        KernelTimer.run('conv_wgrad', fl, 'dmy_conv_wgrad_ex', dt, ptr(x), ptr(dz), ptr(dw), N, H, W, C, xps, K, k, k,
-                        s, p, OH, OW, dzps, flags, stream(), **kw)
+        KernelTimer.run('conv_wgrad', g.flops(), 'dmy_conv_wgrad_ex', dt, ptr(x), ptr(dz), ptr(dw), *g.launch(), dzps,
+                        flags, stream(), **kw)
 
 
 class WgradArena:
@@ -395,24 +412,15 @@ def _fp8_operands(x, xps, weight, spec, wkey, f8in=None):
     """per-tensor e4m3 copy of the activation and the per-output-channel e4m3 weight (cached on the spec until the
     weight changes).  f8in = (x8, amax) emitted by the producer (delayed scaling), else dmy_fp8_quant with the
     current amax"""
-    N, C, H, W = x.shape
-    K, _, KH, KW = weight.shape
-    rows = N * H * W
     if f8in is not None:
-        w8, ws = _fp8_weight(weight, spec, wkey, x.device)
-        return f8in[0], f8in[1], w8, ws
-    x8 = torch.empty(rows * C, dtype=torch.uint8, device=x.device)
-    amax = f32(_F8_WS[0] or _f8_ws(), x.device)  # [0] = the amax the quantisation used
-    call('dmy_fp8_quant', ptr(x), rows, C, xps, ptr(x8), ptr(amax), stream())
-    fc = spec.f8cache
-    if fc is not None and fc[0] == wkey:
-        w8, ws = fc[1], fc[2]
+        x8, amax = f8in
     else:
-        w8 = torch.empty(weight.numel(), dtype=torch.uint8, device=x.device)
-        ws = f32(K, x.device)
-        call('dmy_conv_wprep_fp8', ptr(weight.detach().contiguous()), ptr(w8), ptr(ws), K, C, KH, KW, stream())
-        spec.f8cache = (wkey, w8, ws)
-    return x8, amax, w8, ws
+        N, C, H, W = x.shape
+        rows = N * H * W
+        x8 = torch.empty(rows * C, dtype=torch.uint8, device=x.device)
+        amax = f32(_F8_WS[0] or _f8_ws(), x.device)  # [0] = the amax the quantisation used
+        call('dmy_fp8_quant', ptr(x), rows, C, xps, ptr(x8), ptr(amax), stream())
+    return (x8, amax, *_fp8_weight(weight, spec, wkey, x.device))
 
 
 def prep_weight(w, dtype, need_t, Cp=None):
@@ -426,6 +434,11 @@ def prep_weight(w, dtype, need_t, Cp=None):
 
 
 VW = {torch.float32: 4, torch.bfloat16: 8}
+
+
+def vec_pad(C, dtype):
+    """C rounded up to a whole number of 16-byte vectors of dtype"""
+    return -(-C // VW[dtype]) * VW[dtype]
 
 
 def zero_padded_channels(x):
@@ -485,40 +498,33 @@ class KernelTimer:
                 for k, v in out.items()}
 
 
-def _launch_conv_fwd(x, xps, wf, bias, y, yps, psum, psq, K, k, s, p, OH, OW, Ca, ka, epi=None, f8=None):
-    """(k, s, p) and x's shape are the launch geometry; Ca / ka the layer's real input channels and kernel
-    (they differ for the space-to-depth stem and the channel-padded stem), used for the flop / byte count.
+def _launch_conv_fwd(x, g, wf, bias, y, yps, psum, psq, epi=None, f8=None):
+    """Launch over g's launch geometry; the timer's flops and tag are the layer's real ones (the stem forms differ).
     epi = (scale, shift, act, res, rps): fused inference epilogue (dmy_conv_fwd_act)
     f8 = (x8, amax, w8, wscale): run on the e4m3 kernel (dmy_conv_fwd_fp8, timer kind conv_fwd_f8)"""
-    N, C, H, W = x.shape
-    es = x.element_size()
-    Hi, Wi = (2 * H, 2 * W) if ka != k else (H, W)
-    kw = dict(tag=(N, Ca, Hi, Wi, K, ka, s if ka == k else 2),
-              nbytes=es * (N * H * W * C + K * C * k * k + N * OH * OW * K))
-    fl = 2.0 * N * OH * OW * K * Ca * ka * ka
+    N, C, H, W, K, k, OH, OW = g.N, g.Cg, g.Hg, g.Wg, g.K, g.kg, g.OH, g.OW
+    es, fl, geo = x.element_size(), g.flops(), g.launch()
+    kw = dict(tag=g.tag(), nbytes=es * (N * H * W * C + K * C * k * k + N * OH * OW * K))
+    sc, sh, act, res, rps = epi if epi is not None else (None, None, 0, None, 0)
     if f8 is not None:
         x8, amax, w8, ws = f8
-        sc, sh, act, res, rps = epi if epi is not None else (None, None, 0, None, 0)
         kw['nbytes'] = N * H * W * C + K * C * k * k + es * N * OH * OW * K
         KernelTimer.run('conv_fwd_f8', fl, 'dmy_conv_fwd_fp8', ptr(x8), ptr(w8), ptr(amax), ptr(ws), ptr(bias), ptr(y),
-                        ptr(psum), ptr(psq), N, H, W, C, K, k, k, s, p, OH, OW, yps, ptr(sc), ptr(sh), act, ptr(res),
-                        rps, stream(), **kw)
+                        ptr(psum), ptr(psq), N, H, W, C, K, k, k, g.sg, g.pg, OH, OW, yps, ptr(sc), ptr(sh), act,
+                        ptr(res), rps, stream(), **kw)
         return
-    ne = call('dmy_conv_fwd_splitk_elems', dcode(x), ptr(x), ptr(wf), ptr(y), N, H, W, C, xps, K, k, k, s, p, OH, OW,
-              yps) if psum is None else 0
+    dt = dcode(x)
+    ne = call('dmy_conv_fwd_splitk_elems', dt, ptr(x), ptr(wf), ptr(y), *geo, yps) if psum is None else 0
     if ne > 0:  # small M (batch-1 inference): split-K over the chip, reduced with the epilogue
-        sc, sh, act, res, rps = epi if epi is not None else (None, None, 0, None, 0)
         ws = f32(ne, x.device)
-        KernelTimer.run('conv_fwd', fl, 'dmy_conv_fwd_act_ws', dcode(x), ptr(x), ptr(wf), ptr(bias), ptr(y), N, H, W,
-                        C, xps, K, k, k, s, p, OH, OW, yps, ptr(sc), ptr(sh), act, ptr(res), rps, ptr(ws), ne, stream(),
-                        **kw)
+        KernelTimer.run('conv_fwd', fl, 'dmy_conv_fwd_act_ws', dt, ptr(x), ptr(wf), ptr(bias), ptr(y), *geo, yps,
+                        ptr(sc), ptr(sh), act, ptr(res), rps, ptr(ws), ne, stream(), **kw)
     elif epi is None:
-        KernelTimer.run('conv_fwd', fl, 'dmy_conv_fwd', dcode(x), ptr(x), ptr(wf), ptr(bias), ptr(y), ptr(psum),
-                        ptr(psq), N, H, W, C, xps, K, k, k, s, p, OH, OW, yps, stream(), **kw)
+        KernelTimer.run('conv_fwd', fl, 'dmy_conv_fwd', dt, ptr(x), ptr(wf), ptr(bias), ptr(y), ptr(psum), ptr(psq),
+                        *geo, yps, stream(), **kw)
     else:
-        sc, sh, act, res, rps = epi
-        KernelTimer.run('conv_fwd', fl, 'dmy_conv_fwd_act', dcode(x), ptr(x), ptr(wf), ptr(bias), ptr(y), N, H, W, C,
-                        xps, K, k, k, s, p, OH, OW, yps, ptr(sc), ptr(sh), act, ptr(res), rps, stream(), **kw)
+        KernelTimer.run('conv_fwd', fl, 'dmy_conv_fwd_act', dt, ptr(x), ptr(wf), ptr(bias), ptr(y), *geo, yps, ptr(sc),
+                        ptr(sh), act, ptr(res), rps, stream(), **kw)
 
 
 def eval_coef(spec, dev):
@@ -554,21 +560,201 @@ class BnLink:
 # SCConv's k3 BatchNorm applied by its gate (SCGateFn, dmy_scgate_bn_*): DMY_DEFER_AFFINE=0 restores the separate
 # bn_act_fwd / bn_bwd_reduce passes
 DEFER_AFFINE = [os.environ.get('DMY_DEFER_AFFINE', '1') == '1']
-# backward BN partials (> 256 rows) folded by the two-stage column sum before the finalize (DMY_BWD_COLSUM=0: off)
-BWD_COLSUM = [os.environ.get('DMY_BWD_COLSUM', '1') == '1']
-
-
 # fused 1x1 backward (bwd1x1.hip): BN apply + data-grad + weight-grad of a train-mode 1x1 Conv-BN-act layer in one
 # launch, dz never stored.  DMY_BWD1X1=0 restores the three-pass path (A/B, parity tests)
 BWD1X1 = [os.environ.get('DMY_BWD1X1', '1') == '1']
 
 
-def _bwd1x1(ctx, dy, dps, x, xps, wt, z, scale, shift, mean, invstd, ca, cb, cc, N, C, H, W, K, k, s, p, M):
+def _fold_partials(a, b, P, K, dev):
+    """Two-stage column reduction of two (P, K) partial arrays ahead of a one-block-per-channel finalize, -> (a', b',
+    rows left).  Up to 4096 block rows: the finalize read them with a stride of K floats in 20 us per layer (97 layers
+    per DMA-1536 step); the column sum reads them coalesced.  256 rows or fewer go to the finalize as they are."""
+    if P <= 256:
+        return a, b, P
+    S = call('dmy_colsum2_rows', P)
+    a2, b2 = f32(S * K, dev), f32(S * K, dev)
+    call('dmy_colsum2', ptr(a), ptr(b), P, K, ptr(a2), ptr(b2), stream())
+    return a2, b2, S
+
+
+# ---- the phases of ConvBNActFn: forward in call order, then backward
+
+def _conv_operands(x, weight, spec, need_grad, infer):
+    """-> (x in its launch shape, ConvGeom, wf forward operand, wt data-grad operand or None, wkey) for the three input
+    forms.  wkey is the weight's current value: inference reuses the operand (and the fp8 weight) cached under it."""
+    s2d, cpad = getattr(x, '_dmy_s2d', 0), zero_padded_channels(x)
+    wkey = (PARAM_GEN[0], weight.data_ptr(), weight._version, x.dtype, s2d)
+    wf = spec.wcache[1] if infer and spec.wcache is not None and spec.wcache[0] == wkey else None
+    K, C, k, _ = weight.shape
+    s, p, wt = spec.stride, spec.pad, None
+    x, xps = pixel_stride(x)
+    if s2d:
+        # stem over the space-to-depth image (image_s2d): the k6 s2 p2 conv runs as k3 s1 p1 over Cs channels
+        assert C == s2d and k == 6 and s == 2 and p == 2, 's2d input feeds only the k6 s2 p2 stem'
+        N, Cs, H2, W2 = x.shape
+        g = ConvGeom(N, C, 2 * H2, 2 * W2, xps, K, k, s, p, H2, W2, N * H2 * W2, Cs, H2, W2, 3, 1, 1, C, Cs)
+        if wf is None:
+            wf = torch.empty((K, 9 * Cs), dtype=x.dtype, device=x.device)
+            call('dmy_conv_wprep_s2d', DT[x.dtype], ptr(weight.detach().contiguous()), ptr(wf), K, C, Cs, stream())
+            if infer:
+                spec.wcache = (wkey, wf)
+        return x, g, wf, wt, wkey
+    N, Cx, H, W = x.shape
+    assert Cx == C, (C, Cx)
+    # stem: read the zero-padded storage as Cp channels (16-byte vectors) with zero weights
+    Cp = cpad if (cpad and C % VW[x.dtype] and xps >= cpad) else C
+    OH, OW = conv_out_hw(H, W, k, s, p)
+    g = ConvGeom(N, C, H, W, xps, K, k, s, p, OH, OW, N * OH * OW, Cp, H, W, k, s, p, Cp, 0)
+    pre = WeightPrep.current.get(weight, x.dtype) if WeightPrep.current is not None and Cp == C else None
+    if wf is None and pre is not None:
+        wf, wt = pre
+    elif wf is None:
+        wf, wt = prep_weight(weight, x.dtype, need_grad and Cp == C, Cp)
+        if infer:
+            spec.wcache = (wkey, wf)
+    if Cp != C:
+        x = x.as_strided((N, Cp, H, W), x.stride())
+    return x, g, wf, wt, wkey
+
+
+def _conv_fp8(x, g, weight, spec, wkey, f8in, prod, infer):
+    """e4m3 operands (x8, amax, w8, wscale) when the layer runs on the fp8 kernel, else None.  f8in: the e4m3 copy the
+    producer emitted with the input (delayed scaling); prod: the producer's spec, asked here to start emitting"""
+    if not (spec.fp8 and not g.s2d and g.Cp == g.C and fp8_eligible(g.C, g.K, x.dtype, g.N * g.H * g.W)):
+        return None
+    if f8in is not None and (f8in[0].numel() != g.N * g.H * g.W * g.C or not F8_DELAYED[0]):
+        f8in = None
+    f8 = _fp8_operands(x, g.xps, weight, spec, wkey, f8in)
+    if f8in is None and prod is not None and prod.f8_emit is None and F8_DELAYED[0] and not infer:
+        prod.f8_emit = F8Emit(x.device)  # from the next step on, the producer emits this input's e4m3 copy
+    return f8
+
+
+def _conv_infer(x, g, wf, bias, spec, res, rps, out, yps, f8):
+    """one fused launch: conv + eval-BN + act (+ residual)"""
+    y = out if out is not None else new_act(g.N, g.K, g.OH, g.OW, x)
+    scale, shift = eval_coef(spec, x.device) if spec.bn is not None else (None, None)
+    epi = None if (scale is None and spec.act == ACT_NONE and res is None) else (scale, shift, spec.act, res, rps)
+    _launch_conv_fwd(x, g, wf, bias, y, yps, None, None, epi=epi, f8=f8)
+    return y
+
+
+def _conv_bn_stats(x, g, wf, bias, z, bn, train_bn, f8):
+    """The conv launch into z and the BN coefficients -> (scale, shift, mean, invstd).  Train mode: the launch's
+    epilogue writes per-row partial sums, folded and finalized (dmy_bn_finalize, which also updates the running
+    statistics); eval-mode BN under autograd: scale / shift from the running statistics, mean / invstd unused."""
+    K, M, dev = g.K, g.M, x.device
+    scale, shift, mean, invstd = f32(K, dev), f32(K, dev), f32(K, dev), f32(K, dev)
+    if not train_bn:
+        _launch_conv_fwd(x, g, wf, bias, z, K, None, None, f8=f8)
+        call('dmy_bn_eval_coef', ptr(bn.weight), ptr(bn.bias), ptr(bn.running_mean), ptr(bn.running_var),
+             float(bn.eps), K, ptr(scale), ptr(shift), stream())
+        return scale, shift, mean, invstd
+    # bf16 / fp32: rows for any route; the launch reports the rows its kernel wrote (halo / LANE: per wave)
+    P = call('dmy_conv_fwd_fp8_partial_rows' if f8 is not None else 'dmy_conv_fwd_bound_rows', M, K)
+    psum, psq = f32(P * K, dev), f32(P * K, dev)
+    _launch_conv_fwd(x, g, wf, bias, z, K, psum, psq, f8=f8)
+    if f8 is None:
+        P = call('dmy_conv_fwd_last_rows')
+    psum, psq, P = _fold_partials(psum, psq, P, K, dev)
+    upd = int(bn.training and bn.track_running_stats)
+    if upd:
+        PARAM_GEN[0] += 1  # running stats change behind torch's back: drop inference caches
+    mom = bn.momentum if bn.momentum is not None else 0.0
+    call('dmy_bn_finalize', ptr(psum), ptr(psq), P, K, float(M), ptr(bn.weight), ptr(bn.bias),
+         ptr(bn.running_mean) if upd else None, ptr(bn.running_var) if upd else None,
+         ptr(bn.num_batches_tracked) if upd else None, float(mom), float(bn.eps), upd,
+         ptr(mean), ptr(invstd), ptr(scale), ptr(shift), stream())
+    return scale, shift, mean, invstd
+
+
+def _defer_affine(z, stats, act, K):
+    """Deferred-affine exit: the consumer (SCGateFn) reads z and applies scale / shift itself, and hands this layer's
+    backward the reduce partials through the BnLink returned here; z is valid only for that consumer."""
+    # the link must NOT hold z here: z is this Function's OUTPUT, so ctx -> link -> z -> grad_fn -> ctx would
+    # be a reference cycle through the C++ autograd node that Python's GC cannot break (round 4 leaked
+    # every SCConv's z, ~4 GiB per DMA-1536 step).  The gate receives z as its own input.
+    link = BnLink(*stats, act, K)
+    z._dmy_affine, z._dmy_bnlink = stats, link
+    return link
+
+
+def _act_pass(g, z, scale, shift, spec, res, rps, out, yps, emit_ok):
+    """The activation pass y = act(z * scale + shift) (+ residual), into `out` when given.  emit_ok (a BN layer): when
+    an fp8 consumer asked for it (spec.f8_emit), the pass also emits the e4m3 copy of y, attached as `_dmy_f8`."""
+    K, M = g.K, g.M
+    y = out if out is not None else new_act(g.N, K, g.OH, g.OW, z)
+    emit = spec.f8_emit if (emit_ok and F8_DELAYED[0] and z.dtype == torch.bfloat16 and K % 8 == 0 and yps % 8 == 0 and
+                            (res is None or rps % 8 == 0)) else None
+    if emit is not None and not torch.cuda.is_current_stream_capturing():
+        e8 = emit.run(z, scale, shift, spec.act, res, rps, y, yps, M, K)
+        if e8 is not None:
+            y._dmy_f8 = e8
+    else:
+        call('dmy_bn_act_fwd', dcode(z), ptr(z), K, ptr(scale), ptr(shift), spec.act, ptr(res), rps, ptr(y), yps, M, K,
+             stream())
+    return y
+
+
+def _save_ctx(ctx, saved, g, spec, train_bn, bnlink, weight, bias, gamma, beta, has_res, xsink, rsink):
+    """everything ConvBNActFn.backward reads, set in this one place"""
+    ctx.save_for_backward(*saved)
+    ctx.g, ctx.spec, ctx.train_bn, ctx.bnlink = g, spec, train_bn, bnlink
+    ctx.has_bias, ctx.has_res, ctx.xsink, ctx.rsink = bias is not None, has_res, xsink, rsink
+    ctx.arena, ctx.wkey = WgradArena.current, weight.data_ptr()
+    ctx.pkeys = tuple(t.data_ptr() if t is not None else None for t in (bias, gamma, beta))
+
+
+def _pgrad(ctx, i, K, dev, zero=False):
+    """the gradient tensor of parameter i of (bias, gamma, beta): its (zeroed) arena slice, else a fresh one"""
+    key = ctx.pkeys[i]
+    g = ctx.arena.take(key, (K,)) if (ctx.arena is not None and key is not None) else None
+    return g if g is not None else torch.zeros(K, dtype=torch.float32, device=dev) if zero else f32(K, dev)
+
+
+def _wgrad_target(ctx, shape, dev):
+    """-> (dw, zeroed): the weight's slice of the step's zeroed arena, else a fresh uninitialised tensor"""
+    dw = ctx.arena.take(ctx.wkey, shape) if ctx.arena is not None else None
+    return (dw, True) if dw is not None else (torch.empty(shape, dtype=torch.float32, device=dev), False)
+
+
+def _bn_bwd_coef(ctx, dt, dy, dps, z, stats, gamma):
+    """-> (ca, cb, cc, dgamma, dbeta), the per-channel coefficients dmy_bn_bwd_apply and the fused 1x1 backward take.
+    Train mode: the reduce partials come from the consumer through the BnLink or from dmy_bn_bwd_reduce, are folded,
+    and dmy_bn_bwd_finalize writes the coefficients with dgamma / dbeta.  Eval-mode BN is a fixed affine map: ca =
+    scale, cb = cc = 0, no parameter gradients.  stats = (scale, shift, mean, invstd)."""
+    K, M, dev = ctx.g.K, ctx.g.M, dy.device
+    ca, cb, cc = f32(K, dev), f32(K, dev), f32(K, dev)
+    if not ctx.train_bn:
+        ca.copy_(stats[0])
+        cb.zero_()
+        cc.zero_()
+        return ca, cb, cc, None, None
+    link, rd = ctx.bnlink, None
+    if link is not None:
+        rd, link.ready = link.ready, None
+    if rd is not None and rd[0].data_ptr() == dy.data_ptr() and rd[1] == dps and rd[0]._version == rd[5]:
+        _, _, pdb, pdg, P, _ = rd  # written by the consumer (data-grad epilogue / SCConv gate)
+    else:
+        P = call('dmy_bn_reduce_rows', dt, ptr(z), K, ptr(dy), dps, M, K)
+        pdb, pdg = f32(P * K, dev), f32(P * K, dev)
+        call('dmy_bn_bwd_reduce', dt, ptr(z), K, ptr(dy), dps, *map(ptr, stats), ctx.spec.act, M, K, ptr(pdb),
+             ptr(pdg), stream())
+    pdb, pdg, P = _fold_partials(pdb, pdg, P, K, dev)
+    dgamma, dbeta = _pgrad(ctx, 1, K, dev), _pgrad(ctx, 2, K, dev)
+    call('dmy_bn_bwd_finalize', ptr(pdb), ptr(pdg), P, K, float(M), ptr(gamma), ptr(stats[3]), ptr(dgamma), ptr(dbeta),
+         ptr(ca), ptr(cb), ptr(cc), stream())
+    return ca, cb, cc, dgamma, dbeta
+
+
+def _bwd1x1(ctx, dy, dps, x, wt, z, stats, coef):
     """-> (dx, dw) when the fused kernel took the layer's apply + data-grad + weight-grad, else None.  Eligible: bf16
     storage, train-mode BN, 1x1 stride 1, both gradients wanted, a (K, C) pair the kernel
     is built for (dmy_conv1x1_bwd_bn_ok).  Deterministic mode: the weight-grad partials go through a workspace summed
-    in block order instead of fp32 atomics."""
-    if not (BWD1X1[0] and ctx.train_bn and k == 1 and s == 1 and p == 0 and not ctx.s2d and ctx.cp == C and
+    in block order instead of fp32 atomics.  stats = (scale, shift, mean, invstd), coef = (ca, cb, cc)."""
+    g = ctx.g
+    N, C, H, W, xps, K, M = g.N, g.C, g.H, g.W, g.xps, g.K, g.M
+    if not (BWD1X1[0] and ctx.train_bn and g.k == 1 and g.s == 1 and g.p == 0 and not g.s2d and g.Cp == C and
             dy.dtype == torch.bfloat16 and wt is not None and ctx.needs_input_grad[0] and ctx.needs_input_grad[1]):
         return None
     buf_probe = ctx.xsink.peek(N, C, H, W) if ctx.xsink is not None else None
@@ -576,307 +762,137 @@ def _bwd1x1(ctx, dy, dps, x, xps, wt, z, scale, shift, mean, invstd, ca, cb, cc,
     if not call('dmy_conv1x1_bwd_bn_ok', M, K, C, dps, xps, bps_probe, ptr(dy), ptr(z), ptr(x),
                 ptr(buf_probe[0]) if buf_probe is not None else ptr(z)):
         return None
-    dev = dy.device
     buf, bps, acc = sink_target(ctx.xsink, N, C, H, W, z)
-    dw = ctx.arena.take(ctx.wkey, (K, C, 1, 1)) if ctx.arena is not None else None
-    if dw is None:
-        dw = torch.zeros((K, C, 1, 1), dtype=torch.float32, device=dev)
-    es = z.element_size()
+    dw, zeroed = _wgrad_target(ctx, (K, C, 1, 1), dy.device)
+    if not zeroed:  # the kernel accumulates
+        dw.zero_()
     ne = call('dmy_conv1x1_bwd_bn_ws_elems', M, K, C) if DETERMINISTIC[0] else 0
-    ws = f32(ne, dev) if ne else None
+    ws = f32(ne, dy.device) if ne else None
     KernelTimer.run('conv_bwd1x1', 4.0 * M * K * C, 'dmy_conv1x1_bwd_bn', ptr(dy), dps, ptr(z), ptr(x), xps, ptr(wt),
-                    ptr(scale), ptr(shift), ptr(mean), ptr(invstd), ctx.spec.act, ptr(ca), ptr(cb), ptr(cc), ptr(buf),
-                    bps, acc, ptr(dw), ptr(ws), ne, M, K, C, stream(), tag=(N, C, H, W, K, k, s),
-                    nbytes=es * (2 * M * K + (2 + acc) * M * C + K * C) + 4 * K * C)
+                    *map(ptr, stats), ctx.spec.act, *map(ptr, coef), ptr(buf), bps, acc, ptr(dw), ptr(ws), ne, M, K, C,
+                    stream(), tag=g.tag(),
+                    nbytes=z.element_size() * (2 * M * K + (2 + acc) * M * C + K * C) + 4 * K * C)
     return sink_result(ctx.xsink, buf), dw
+
+
+def _act_bias_bwd(ctx, dt, dy, dps, z):
+    """layer without BN -> (dz, its pixel stride, dbias): the activation's backward (dmy_bn_bwd_apply with the identity
+    affine map; dz is dy itself behind ACT_NONE) and the bias gradient, the column sums of dz"""
+    K, M, dev = ctx.g.K, ctx.g.M, dy.device
+    dz, dzps, dbias = dy, dps, None
+    if ctx.spec.act != ACT_NONE:
+        dz, dzps = new_act(ctx.g.N, K, ctx.g.OH, ctx.g.OW, z), K
+        zero, one = const_vec(K, 0.0, dev), const_vec(K, 1.0, dev)
+        call('dmy_bn_bwd_apply', dt, ptr(z), K, ptr(dy), dps, ptr(one), ptr(zero), ptr(zero), ptr(one),
+             ctx.spec.act, ptr(one), ptr(zero), ptr(zero), ptr(dz), K, M, K, stream())
+    if ctx.has_bias:
+        P = call('dmy_bn_reduce_rows', dt, ptr(dz), dzps, None, 0, M, K)
+        ps_, pq_ = f32(P * K, dev), f32(P * K, dev)
+        call('dmy_bn_stats', dt, ptr(dz), dzps, M, K, ptr(ps_), ptr(pq_), stream())
+        dbias = _pgrad(ctx, 0, K, dev)
+        call('dmy_reduce_rows', ptr(ps_), P, K, ptr(dbias), 0, stream())
+    return dz, dzps, dbias
+
+
+def _dgrad(ctx, dt, dz, dzps, wt, z):
+    """the data-grad launch, into the input's GradSink when it has one"""
+    g = ctx.g
+    N, C, H, W, K, k, M = g.N, g.C, g.H, g.W, g.K, g.k, g.M
+    if g.Cp != C or g.s2d:
+        raise NotImplementedError('input gradient of a channel-padded stem conv')
+    buf, bps, acc = sink_target(ctx.xsink, N, C, H, W, z)
+    KernelTimer.run('conv_dgrad', g.flops(), 'dmy_conv_dgrad', dt, ptr(dz), ptr(wt), ptr(buf), acc, N, H, W, C, bps, K,
+                    k, k, g.s, g.p, g.OH, g.OW, dzps, stream(), tag=g.tag(),
+                    nbytes=z.element_size() * (M * K + K * C * k * k + (1 + acc) * N * H * W * C))
+    return sink_result(ctx.xsink, buf)
+
+
+def _conv_wgrad(ctx, dt, x, dz, dzps):
+    """the weight gradient in torch OIHW order, in the weight's arena slice when it has one"""
+    g = ctx.g
+    K, C, k, dev = g.K, g.C, g.k, dz.device
+    dw, zeroed = _wgrad_target(ctx, (K, C, k, k), dev)
+    if g.s2d:
+        dwo = f32(K * 9 * g.s2d, dev)
+        _wgrad(dt, x, dz, dzps, dwo, g, 0)
+        call('dmy_conv_wgrad_s2d_to_oihw', ptr(dwo), ptr(dw), K, C, g.s2d, stream())
+    elif k == 1 and g.Cp == C:
+        # 1x1: the GEMM view IS torch OIHW -> accumulate straight into the step's zeroed arena slice
+        _wgrad(dt, x, dz, dzps, dw, g, WGRAD_OIHW | (WGRAD_ZEROED if zeroed else 0))
+    else:
+        # k > 1: OIHW-order atomics would scatter every tile row with stride k*k (measured 1.5x slower
+        # weight-grad on yolov5s); accumulate in GEMM order, then one layout pass (drops stem padding)
+        dwo = f32(K * g.Cp * k * k, dev)
+        _wgrad(dt, x, dz, dzps, dwo, g, 0)
+        call('dmy_conv_wgrad_to_oihw', ptr(dwo), ptr(dw), K, C, g.Cp, k, k, stream())
+    return dw
 
 
 class ConvBNActFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, x, weight, bias, gamma, beta, res, spec, xsink=None, rsink=None, grad_on=True):
-        s2d = getattr(x, '_dmy_s2d', 0)
+    def forward(ctx, x, weight, bias, gamma, beta, res, spec, xsink=None, rsink=None, grad_on=True, out=None):
+        """out: None or [view] -- see out_view; ignored by a layer with no separate activation pass"""
         f8in, prod = getattr(x, '_dmy_f8', None), getattr(x, '_dmy_prod', None)
-        out_req, _OUT[0] = _OUT[0], None  # conv_bn_act's out view, checked against the output geometry below
-        K, C2, k, _ = weight.shape
-        ctx.s2d = 0
         # ctx.needs_input_grad mirrors requires_grad even when the CALLER runs under torch.no_grad() (forward itself
         # always runs with grad disabled): `grad_on` is the caller's grad mode, so a no-grad call (detect / val with
         # parameters that require grad) takes the one-launch inference path
         need_grad = grad_on and any(ctx.needs_input_grad[:6])
         bn = spec.bn
         train_bn = bn is not None and (bn.training or not bn.track_running_stats)
-        infer = not need_grad and not train_bn  # one fused launch: conv + eval-BN + act (+ residual)
-        wkey = (PARAM_GEN[0], weight.data_ptr(), weight._version, x.dtype, s2d)
-        cached = infer and spec.wcache is not None and spec.wcache[0] == wkey
-        if s2d:
-            # stem over the space-to-depth image (image_s2d): the k6 s2 p2 conv runs as k3 s1 p1 over Cs channels
-            assert C2 == s2d and k == 6 and spec.stride == 2 and spec.pad == 2, 's2d input feeds only the k6 s2 p2 stem'
-            x, xps = pixel_stride(x)
-            N, Cs, H2, W2 = x.shape
-            C, H, W = s2d, 2 * H2, 2 * W2
-            OH, OW = H2, W2
-            if cached:
-                wf = spec.wcache[1]
-            else:
-                wf = torch.empty((K, 9 * Cs), dtype=x.dtype, device=x.device)
-                call('dmy_conv_wprep_s2d', DT[x.dtype], ptr(weight.detach().contiguous()), ptr(wf), K, C, Cs, stream())
-                if infer:
-                    spec.wcache = (wkey, wf)
-            wt = None
-            ctx.s2d = Cs
-            # from here on the launch geometry is the k3 s1 p1 view
-            Cg, Hg, Wg, kg, sg, pg = Cs, H2, W2, 3, 1, 1
-            Cp = C
-        else:
-            cpad = zero_padded_channels(x)
-            x, xps = pixel_stride(x)
-            N, C, H, W = x.shape
-            assert C2 == C, (C2, C)
-            # stem: read the zero-padded storage as Cp channels (16-byte vectors) with zero weights
-            Cp = cpad if (cpad and C % VW[x.dtype] and xps >= cpad) else C
-            OH, OW = conv_out_hw(H, W, k, spec.stride, spec.pad)
-            pre = WeightPrep.current.get(weight, x.dtype) if WeightPrep.current is not None and Cp == C else None
-            if cached:
-                wf, wt = spec.wcache[1], None
-            elif pre is not None:
-                wf, wt = pre
-            else:
-                wf, wt = prep_weight(weight, x.dtype, need_grad and Cp == C, Cp)
-                if infer:
-                    spec.wcache = (wkey, wf)
-            if Cp != C:
-                x = x.as_strided((N, Cp, H, W), x.stride())
-            Cg, Hg, Wg, kg, sg, pg = Cp, H, W, k, spec.stride, spec.pad
-        s, p = spec.stride, spec.pad
-        dev, dt = x.device, x.dtype
-        M = N * OH * OW
-        f8 = None
-        if spec.fp8 and not s2d and Cp == C and fp8_eligible(C, K, dt, N * H * W):
-            if f8in is not None and (f8in[0].numel() != N * H * W * C or not F8_DELAYED[0]):
-                f8in = None
-            f8 = _fp8_operands(x, xps, weight, spec, wkey, f8in)
-            if f8in is None and prod is not None and prod.f8_emit is None and F8_DELAYED[0] and not infer:
-                prod.f8_emit = F8Emit(dev)  # from the next step on, the producer emits this input's e4m3 copy
-        if res is not None:
-            res, rps = pixel_stride(res)
-        else:
-            rps = 0
-        _OUT[0] = out_req
-        out = _take_out(N, K, OH, OW, x) if (bn is not None or spec.act != ACT_NONE or res is not None) else None
-        yps = pixel_stride(out)[1] if out is not None else K
+        infer = not need_grad and not train_bn
+        x, g, wf, wt, wkey = _conv_operands(x, weight, spec, need_grad, infer)
+        f8 = _conv_fp8(x, g, weight, spec, wkey, f8in, prod, infer)
+        res, rps = pixel_stride(res) if res is not None else (None, 0)
+        act_pass = bn is not None or spec.act != ACT_NONE or res is not None
+        out, yps = out_view(out and out[0], (g.N, g.K, g.OH, g.OW), x) if act_pass else (None, None)
+        yps = g.K if out is None else yps
         if infer:
-            y = out if out is not None else new_act(N, K, OH, OW, x)
-            scale, shift = eval_coef(spec, dev) if bn is not None else (None, None)
-            if scale is None and spec.act == ACT_NONE and res is None:
-                _launch_conv_fwd(x, xps, wf, bias, y, yps, None, None, K, kg, sg, pg, OH, OW, C, k, f8=f8)
-            else:
-                _launch_conv_fwd(x, xps, wf, bias, y, yps, None, None, K, kg, sg, pg, OH, OW, C, k,
-                                 epi=(scale, shift, spec.act, res, rps), f8=f8)
-            return y
-        z = new_act(N, K, OH, OW, x)
-        if bn is not None:
-            scale, shift, mean, invstd = f32(K, dev), f32(K, dev), f32(K, dev), f32(K, dev)
-            if train_bn:
-                if f8 is not None:
-                    P = call('dmy_conv_fwd_fp8_partial_rows', M, K)
-                else:  # rows for any route; the launch reports the rows its kernel wrote (halo / LANE: per wave)
-                    P = call('dmy_conv_fwd_bound_rows', M, K)
-                psum, psq = f32(P * K, dev), f32(P * K, dev)
-                _launch_conv_fwd(x, xps, wf, bias, z, K, psum, psq, K, kg, sg, pg, OH, OW, C, k, f8=f8)
-                if f8 is None:
-                    P = call('dmy_conv_fwd_last_rows')
-                if P > 256:  # two-stage column reduction of the epilogue partials
-                    S = call('dmy_colsum2_rows', P)
-                    ps2, pq2 = f32(S * K, dev), f32(S * K, dev)
-                    call('dmy_colsum2', ptr(psum), ptr(psq), P, K, ptr(ps2), ptr(pq2), stream())
-                    psum, psq, P = ps2, pq2, S
-                upd = int(bn.training and bn.track_running_stats)
-                if upd:
-                    PARAM_GEN[0] += 1  # running stats change behind torch's back: drop inference caches
-                mom = bn.momentum if bn.momentum is not None else 0.0
-                call('dmy_bn_finalize', ptr(psum), ptr(psq), P, K, float(M), ptr(bn.weight), ptr(bn.bias),
-                     ptr(bn.running_mean) if upd else None, ptr(bn.running_var) if upd else None,
-                     ptr(bn.num_batches_tracked) if upd else None, float(mom), float(bn.eps), upd,
-                     ptr(mean), ptr(invstd), ptr(scale), ptr(shift), stream())
-            else:
-                _launch_conv_fwd(x, xps, wf, bias, z, K, None, None, K, kg, sg, pg, OH, OW, C, k, f8=f8)
-                call('dmy_bn_eval_coef', ptr(bn.weight), ptr(bn.bias), ptr(bn.running_mean), ptr(bn.running_var),
-                     float(bn.eps), K, ptr(scale), ptr(shift), stream())
-            defer = (spec.defer and DEFER_AFFINE[0] and train_bn and need_grad and dt == torch.bfloat16 and
-                     spec.act == ACT_NONE and res is None and out is None and K % 8 == 0 and f8 is None)
-            if defer:
-                # the consumer (SCGateFn) reads z and applies scale / shift itself, and hands this layer's backward the
-                # reduce partials (BnLink): the tensor returned is z, valid only for that consumer
-                ctx.save_for_backward(x, wt, z, scale, shift, mean, invstd, bn.weight if bn.weight is not None else None)
-                # the link must NOT hold z here: z is this Function's OUTPUT, so ctx -> link -> z -> grad_fn -> ctx would
-                # be a reference cycle through the C++ autograd node that Python's GC cannot break (round 4 leaked
-                # every SCConv's z, ~4 GiB per DMA-1536 step).  The gate receives z as its own input.
-                ctx.bnlink = BnLink(scale, shift, mean, invstd, spec.act, K)
-                z._dmy_affine, z._dmy_bnlink = (scale, shift, mean, invstd), ctx.bnlink
-                ctx.spec, ctx.train_bn, ctx.has_res = spec, train_bn, False
-                ctx.geom = (N, C, H, W, xps, K, k, s, p, OH, OW)
-                ctx.ggeom = (Hg, Wg, kg, sg, pg)
-                ctx.cp = Cp
-                ctx.has_bias = bias is not None
-                ctx.xsink, ctx.rsink = xsink, rsink
-                ctx.arena = WgradArena.current
-                ctx.wkey = weight.data_ptr()
-                ctx.pkeys = tuple(t.data_ptr() if t is not None else None for t in (bias, gamma, beta))
-                return z
-            y = out if out is not None else new_act(N, K, OH, OW, x)
-            emit = spec.f8_emit if (F8_DELAYED[0] and dt == torch.bfloat16 and K % 8 == 0 and yps % 8 == 0 and
-                                    (res is None or rps % 8 == 0)) else None
-            if emit is not None and not torch.cuda.is_current_stream_capturing():
-                e8 = emit.run(z, scale, shift, spec.act, res, rps, y, yps, M, K)
-                if e8 is not None:
-                    y._dmy_f8 = e8
-            else:
-                call('dmy_bn_act_fwd', dcode(x), ptr(z), K, ptr(scale), ptr(shift), spec.act, ptr(res), rps, ptr(y),
-                     yps, M, K, stream())
-            if dt == torch.bfloat16 and K % 128 == 0 and train_bn:
-                y._dmy_prod = spec  # an fp8 consumer may ask this layer to emit its e4m3 copy (F8Emit)
-            ctx.save_for_backward(x, wt, z, scale, shift, mean, invstd, bn.weight if bn.weight is not None else None)
-            ctx.bnlink = None
+            return _conv_infer(x, g, wf, bias, spec, res, rps, out, yps, f8)
+        z, link = new_act(g.N, g.K, g.OH, g.OW, x), None
+        if bn is None:
+            _launch_conv_fwd(x, g, wf, bias, z, g.K, None, None, f8=f8)
+            y = _act_pass(g, z, const_vec(g.K, 1.0, x.device), const_vec(g.K, 0.0, x.device), spec, res, rps, out, yps,
+                          False) if act_pass else z
+            saved = (x, wt, z)
         else:
-            _launch_conv_fwd(x, xps, wf, bias, z, K, None, None, K, kg, sg, pg, OH, OW, C, k, f8=f8)
-            if spec.act != ACT_NONE or res is not None:
-                y = out if out is not None else new_act(N, K, OH, OW, x)
-                one, zero = const_vec(K, 1.0, dev), const_vec(K, 0.0, dev)
-                call('dmy_bn_act_fwd', dcode(x), ptr(z), K, ptr(one), ptr(zero), spec.act, ptr(res), rps, ptr(y), yps,
-                     M, K, stream())
+            stats = _conv_bn_stats(x, g, wf, bias, z, bn, train_bn, f8)
+            saved = (x, wt, z, *stats, bn.weight)
+            if (spec.defer and DEFER_AFFINE[0] and train_bn and need_grad and x.dtype == torch.bfloat16 and
+                    spec.act == ACT_NONE and res is None and out is None and g.K % 8 == 0 and f8 is None):
+                y, link = z, _defer_affine(z, stats, spec.act, g.K)
             else:
-                y = z
-            ctx.save_for_backward(x, wt, z)
-        ctx.spec, ctx.train_bn, ctx.has_res = spec, train_bn, res is not None
-        ctx.geom = (N, C, H, W, xps, K, k, s, p, OH, OW)
-        ctx.ggeom = (Hg, Wg, kg, sg, pg)
-        ctx.cp = Cp
-        ctx.has_bias = bias is not None
-        ctx.xsink, ctx.rsink = xsink, rsink
-        ctx.arena = WgradArena.current
-        ctx.wkey = weight.data_ptr()
-        ctx.pkeys = tuple(t.data_ptr() if t is not None else None for t in (bias, gamma, beta))
+                y = _act_pass(g, z, stats[0], stats[1], spec, res, rps, out, yps, True)
+                if x.dtype == torch.bfloat16 and g.K % 128 == 0 and train_bn:
+                    y._dmy_prod = spec  # an fp8 consumer may ask this layer to emit its e4m3 copy (F8Emit)
+        _save_ctx(ctx, saved, g, spec, train_bn, link, weight, bias, gamma, beta, res is not None, xsink, rsink)
         return y
 
     @staticmethod
     def backward(ctx, dy):
-        spec = ctx.spec
-        N, C, H, W, xps, K, k, s, p, OH, OW = ctx.geom
-        dy, dps = pixel_stride(dy.to(ctx.saved_tensors[2].dtype))
-        dev = dy.device
-        M = N * OH * OW
-        dt = dcode(dy)
-        dbias = dgamma = dbeta = None
-        arena = ctx.arena
-
-        def pgrad(key, zero=False):
-            """the parameter's gradient tensor: its (zeroed) arena slice, else a fresh one"""
-            g = arena.take(key, (K,)) if (arena is not None and key is not None) else None
-            if g is None:
-                g = torch.zeros(K, dtype=torch.float32, device=dev) if zero else f32(K, dev)
-            return g
-
+        g, spec = ctx.g, ctx.spec
+        x, wt, z, *bnt = ctx.saved_tensors
+        dy, dps = pixel_stride(dy.to(z.dtype))
+        K, dev, dt = g.K, dy.device, dcode(dy)
+        dbias = dgamma = dbeta = fused = None
         if spec.bn is not None:
-            x, wt, z, scale, shift, mean, invstd, gamma = ctx.saved_tensors
-            dz = new_act(N, K, OH, OW, z)
-            ca, cb, cc = f32(K, dev), f32(K, dev), f32(K, dev)
-            if ctx.train_bn:
-                link = getattr(ctx, 'bnlink', None)
-                rd = link.ready if link is not None else None
-                if link is not None:
-                    link.ready = None
-                if rd is not None and rd[0].data_ptr() == dy.data_ptr() and rd[1] == dps and \
-                        rd[0]._version == rd[5]:
-                    _, _, pdb, pdg, P, _ = rd  # written by the consumer (data-grad epilogue / SCConv gate)
-                else:
-                    P = call('dmy_bn_reduce_rows', dt, ptr(z), K, ptr(dy), dps, M, K)
-                    pdb, pdg = f32(P * K, dev), f32(P * K, dev)
-                    call('dmy_bn_bwd_reduce', dt, ptr(z), K, ptr(dy), dps, ptr(scale), ptr(shift), ptr(mean),
-                         ptr(invstd), spec.act, M, K, ptr(pdb), ptr(pdg), stream())
-                if P > 256 and BWD_COLSUM[0]:
-                    # up to 4096 block rows: the one-block-per-channel finalize read them with a stride of K floats in
-                    # 20 us per layer (97 layers per DMA-1536 step); the two-stage column sum reads them coalesced
-                    S = call('dmy_colsum2_rows', P)
-                    pd2, pg2 = f32(S * K, dev), f32(S * K, dev)
-                    call('dmy_colsum2', ptr(pdb), ptr(pdg), P, K, ptr(pd2), ptr(pg2), stream())
-                    pdb, pdg, P = pd2, pg2, S
-                dgamma, dbeta = pgrad(ctx.pkeys[1]), pgrad(ctx.pkeys[2])
-                call('dmy_bn_bwd_finalize', ptr(pdb), ptr(pdg), P, K, float(M), ptr(gamma), ptr(invstd), ptr(dgamma),
-                     ptr(dbeta), ptr(ca), ptr(cb), ptr(cc), stream())
-            else:
-                ca.copy_(scale)
-                cb.zero_()
-                cc.zero_()
-            fused = _bwd1x1(ctx, dy, dps, x, xps, wt, z, scale, shift, mean, invstd, ca, cb, cc, N, C, H, W, K, k, s,
-                            p, M)
-            if fused is not None:
-                dx, dw = fused
-                dbias = pgrad(ctx.pkeys[0], zero=True) if ctx.has_bias else None  # sum(dz) == 0 behind train-mode BN
-                dres = (dy if ctx.rsink is None else ctx.rsink.passthrough(dy)) if ctx.has_res else None
-                return dx, dw, dbias, dgamma, dbeta, dres, None, None, None, None
-            call('dmy_bn_bwd_apply', dt, ptr(z), K, ptr(dy), dps, ptr(scale), ptr(shift), ptr(mean), ptr(invstd),
-                 spec.act, ptr(ca), ptr(cb), ptr(cc), ptr(dz), K, M, K, stream())
-            dzps = K
+            *stats, gamma = bnt
+            *coef, dgamma, dbeta = _bn_bwd_coef(ctx, dt, dy, dps, z, stats, gamma)
+            fused = _bwd1x1(ctx, dy, dps, x, wt, z, stats, coef)
+            if fused is None:
+                dz, dzps = new_act(g.N, K, g.OH, g.OW, z), K
+                call('dmy_bn_bwd_apply', dt, ptr(z), K, ptr(dy), dps, *map(ptr, stats), spec.act, *map(ptr, coef),
+                     ptr(dz), K, g.M, K, stream())
+            if ctx.has_bias and ctx.train_bn:
+                dbias = _pgrad(ctx, 0, K, dev, zero=True)  # sum(dz) == 0 exactly behind train-mode BN
         else:
-            x, wt, z = ctx.saved_tensors
-            if spec.act != ACT_NONE:
-                dz = new_act(N, K, OH, OW, z)
-                zero, one = const_vec(K, 0.0, dev), const_vec(K, 1.0, dev)
-                call('dmy_bn_bwd_apply', dt, ptr(z), K, ptr(dy), dps, ptr(one), ptr(zero), ptr(zero), ptr(one),
-                     spec.act, ptr(one), ptr(zero), ptr(zero), ptr(dz), K, M, K, stream())
-                dzps = K
-            else:
-                dz, dzps = dy, dps
-            if ctx.has_bias:
-                P = call('dmy_bn_reduce_rows', dt, ptr(dz), dzps, None, 0, M, K)
-                ps_, pq_ = f32(P * K, dev), f32(P * K, dev)
-                call('dmy_bn_stats', dt, ptr(dz), dzps, M, K, ptr(ps_), ptr(pq_), stream())
-                dbias = pgrad(ctx.pkeys[0])
-                call('dmy_reduce_rows', ptr(ps_), P, K, ptr(dbias), 0, stream())
-        if spec.bn is not None and ctx.has_bias and ctx.train_bn:
-            dbias = pgrad(ctx.pkeys[0], zero=True)  # sum(dz) == 0 exactly behind train-mode BN
-        dx = dw = None
-        Cp = ctx.cp
-        if ctx.needs_input_grad[0]:
-            if Cp != C or ctx.s2d:
-                raise NotImplementedError('input gradient of a channel-padded stem conv')
-            buf, bps, acc = sink_target(ctx.xsink, N, C, H, W, z)
-            kw = dict(tag=(N, C, H, W, K, k, s),
-                      nbytes=z.element_size() * (M * K + K * C * k * k + (1 + acc) * N * H * W * C))
-            fl = 2.0 * M * K * C * k * k
-            KernelTimer.run('conv_dgrad', fl, 'dmy_conv_dgrad', dt, ptr(dz), ptr(wt), ptr(buf), acc, N, H, W, C, bps,
-                            K, k, k, s, p, OH, OW, dzps, stream(), **kw)
-            dx = sink_result(ctx.xsink, buf)
-        if ctx.needs_input_grad[1] and ctx.s2d:
-            Cs = ctx.s2d
-            H2, W2 = ctx.ggeom[:2]
-            dwo = f32(K * 9 * Cs, dev)
-            _wgrad(dt, x, dz, dwo, N, H2, W2, Cs, xps, K, 3, 1, 1, OH, OW, dzps, 0, 2.0 * M * K * C * k * k,
-                   tag=(N, C, H, W, K, k, s), nbytes=z.element_size() * (N * H2 * W2 * Cs + M * K) + 4 * K * Cs * 9)
-            dw = ctx.arena.take(ctx.wkey, (K, C, k, k)) if ctx.arena is not None else None
-            if dw is None:
-                dw = torch.empty((K, C, k, k), dtype=torch.float32, device=dev)
-            call('dmy_conv_wgrad_s2d_to_oihw', ptr(dwo), ptr(dw), K, C, Cs, stream())
-        elif ctx.needs_input_grad[1]:
-            wkw = dict(tag=(N, C, H, W, K, k, s), nbytes=z.element_size() * (N * H * W * Cp + M * K) + 4 * K * Cp * k * k)
-            dw = ctx.arena.take(ctx.wkey, (K, C, k, k)) if ctx.arena is not None else None
-            zeroed = dw is not None
-            if dw is None:
-                dw = torch.empty((K, C, k, k), dtype=torch.float32, device=dev)
-            if k == 1 and Cp == C:
-                # 1x1: the GEMM view IS torch OIHW -> accumulate straight into the step's zeroed arena slice
-                flags = WGRAD_OIHW | (WGRAD_ZEROED if zeroed else 0)
-                _wgrad(dt, x, dz, dw, N, H, W, C, xps, K, k, s, p, OH, OW, dzps, flags, 2.0 * M * K * C * k * k, **wkw)
-            else:
-                # k > 1: OIHW-order atomics would scatter every tile row with stride k*k (measured 1.5x slower
-                # weight-grad on yolov5s); accumulate in GEMM order, then one layout pass (drops stem padding)
-                dwo = f32(K * Cp * k * k, dev)
-                _wgrad(dt, x, dz, dwo, N, H, W, Cp, xps, K, k, s, p, OH, OW, dzps, 0, 2.0 * M * K * C * k * k, **wkw)
-                call('dmy_conv_wgrad_to_oihw', ptr(dwo), ptr(dw), K, C, Cp, k, k, stream())
-        dres = None
-        if ctx.has_res:
-            dres = dy if ctx.rsink is None else ctx.rsink.passthrough(dy)
-        return dx, dw, dbias, dgamma, dbeta, dres, None, None, None, None
+            dz, dzps, dbias = _act_bias_bwd(ctx, dt, dy, dps, z)
+        if fused is not None:
+            dx, dw = fused
+        else:
+            dx = _dgrad(ctx, dt, dz, dzps, wt, z) if ctx.needs_input_grad[0] else None
+            dw = _conv_wgrad(ctx, dt, x, dz, dzps) if ctx.needs_input_grad[1] else None
+        dres = (dy if ctx.rsink is None else ctx.rsink.passthrough(dy)) if ctx.has_res else None
+        return dx, dw, dbias, dgamma, dbeta, dres, None, None, None, None, None
 
 
 def conv_bn_act(x, weight, bias, bn, stride, pad, act, res=None, spec=None, xsink=None, rsink=None, out=None,
@@ -890,11 +906,8 @@ def conv_bn_act(x, weight, bias, bn, stride, pad, act, res=None, spec=None, xsin
     spec.defer = bool(defer)
     gamma = bn.weight if bn is not None else None
     beta = bn.bias if bn is not None else None
-    _OUT[0] = out
-    try:
-        return ConvBNActFn.apply(x, weight, bias, gamma, beta, res, spec, xsink, rsink, torch.is_grad_enabled())
-    finally:
-        _OUT[0] = None
+    return ConvBNActFn.apply(x, weight, bias, gamma, beta, res, spec, xsink, rsink, torch.is_grad_enabled(),
+                             [out] if out is not None else None)
 
 
 # ------------------------------------------------------------------ pooling / resize / concat
@@ -906,10 +919,9 @@ class MaxPoolFn(torch.autograd.Function):
         list so autograd does not treat the buffer as an input"""
         x, xps = pixel_stride(x)
         N, C, H, W = x.shape
-        o = out[0] if out else None
-        if o is not None and (tuple(o.shape) != (N, C, H, W) or o.dtype != x.dtype or pixel_stride(o)[0] is not o):
-            o = None
-        y, yps = (o, pixel_stride(o)[1]) if o is not None else (new_act(N, C, H, W, x), C)
+        y, yps = out_view(out and out[0], (N, C, H, W), x)
+        if y is None:
+            y, yps = new_act(N, C, H, W, x), C
         arg = torch.empty((N, H, W, C), dtype=torch.uint8, device=x.device)
         call('dmy_maxpool_fwd', dcode(x), ptr(x), xps, ptr(y), yps, ptr(arg), N, H, W, C, k, stream())
         ctx.save_for_backward(arg)
@@ -926,28 +938,21 @@ class MaxPoolFn(torch.autograd.Function):
         return sink_result(ctx.sink, buf), None, None, None
 
 
-POOL3 = [os.environ.get('DMY_POOL3', '1') == '1']  # the one-launch pyramid (DMY_POOL3=0: three MaxPoolFn launches)
-
-
 def maxpool_chain3(x, k, outs=(None, None, None)):
     """inference SPPF / SPPFCSPC pyramid: (pool(x), pool(pool(x)), pool(pool(pool(x)))) with the k x k stride-1 pool in
     ONE launch (dmy_maxpool_chain3_fwd, the bits of three MaxPoolFn launches), written into `outs` when they are three
     NHWC views with one pixel stride (concat_buffer slices), else into fresh tensors.  None when autograd is recording
     (the backward needs MaxPoolFn's argmax) or the kernel does not take the shape: the caller chains MaxPoolFn"""
-    if torch.is_grad_enabled() or k not in (3, 5) or x.dtype not in (torch.bfloat16, torch.float32) or not POOL3[0]:
+    if torch.is_grad_enabled() or k not in (3, 5) or x.dtype not in (torch.bfloat16, torch.float32):
         return None
     x, xps = pixel_stride(x)
     N, C, H, W = x.shape
-    vw = 8 if x.dtype == torch.bfloat16 else 4
-    ys, yps = [], None
-    for o in outs:
-        if o is None or tuple(o.shape) != (N, C, H, W) or o.dtype != x.dtype or pixel_stride(o)[0] is not o or \
-                (yps is not None and pixel_stride(o)[1] != yps):
-            ys = None
-            break
-        yps = pixel_stride(o)[1]
-        ys.append(o)
-    if ys is None:
+    vw = VW[x.dtype]
+    views = [out_view(o, (N, C, H, W), x) for o in outs]
+    yps = views[0][1]
+    if yps is not None and all(ps == yps for _, ps in views):  # three valid views with one pixel stride
+        ys = [v for v, _ in views]
+    else:
         ys, yps = [new_act(N, C, H, W, x) for _ in range(3)], C
     if C % vw or xps % vw or yps % vw or N * (C // vw) >= 65536 or any(t.data_ptr() % 16 for t in [x] + ys):
         return None
@@ -983,10 +988,9 @@ class ResizeFn(torch.autograd.Function):
         """out: None or [view] -- a concat_buffer channel slice the result is written into (Model's concat plan)"""
         x, xps = pixel_stride(x)
         N, C, H, W = x.shape
-        o = out[0] if out else None
-        if o is not None and (tuple(o.shape) != (N, C, OH, OW) or o.dtype != x.dtype or pixel_stride(o)[0] is not o):
-            o = None
-        y, yps = (o, pixel_stride(o)[1]) if o is not None else (new_act(N, C, OH, OW, x), C)
+        y, yps = out_view(out and out[0], (N, C, OH, OW), x)
+        if y is None:
+            y, yps = new_act(N, C, OH, OW, x), C
         call('dmy_resize_fwd', dcode(x), ptr(x), xps, ptr(y), yps, 1.0, N, H, W, OH, OW, C, stream())
         ctx.shape = (N, C, H, W, OH, OW)
         return y
@@ -998,9 +1002,6 @@ class ResizeFn(torch.autograd.Function):
         dx = new_act(N, C, H, W, dy)
         call('dmy_resize_bwd', dcode(dy), ptr(dy), dps, ptr(dx), C, N, H, W, OH, OW, C, stream())
         return dx, None, None, None
-
-
-CAT_DOT = [os.environ.get('DMY_CAT_DOT', '1') == '1']  # weighted-concat backward in one pass per input
 
 
 class ConcatFn(torch.autograd.Function):
@@ -1054,7 +1055,7 @@ class ConcatFn(torch.autograd.Function):
             g, gps, acc = sink_target(sinks[i], N, C, H, W, dy)
             sl = dy[:, c0:c0 + C]
             vw = 8 if dy.dtype == torch.bfloat16 else 4
-            if CAT_DOT[0] and C % vw == 0 and dps % vw == 0 and gps % vw == 0 and xps % vw == 0 and \
+            if C % vw == 0 and dps % vw == 0 and gps % vw == 0 and xps % vw == 0 and \
                     all(t.data_ptr() % 16 == 0 for t in (sl, g, x)):  # one pass over the dy slice
                 call('dmy_slice_copy_dot', dcode(dy), ptr(sl), dps, ptr(g), gps, ptr(x), xps, M, C, ptr(w), i, len(xs),
                      float(ctx.eps), acc, ptr(part[i]), stream())
@@ -1216,18 +1217,23 @@ class AddFn(torch.autograd.Function):
         return da, dy, None
 
 
+def _image_src(x):
+    """-> (contiguous source, kind, scale) of an NCHW image for the image kernels: uint8 (kind 0) is scaled by 1 / 255,
+    any float image is read as fp32 (kind 1) unscaled"""
+    xc = x.contiguous()
+    if x.dtype == torch.uint8:
+        return xc, 0, 1.0 / 255.0
+    return (xc if xc.dtype == torch.float32 else xc.float()), 1, 1.0
+
+
 def image_s2d(x, dtype):
     """NCHW image (uint8 -> /255, or float) -> space-to-depth NHWC storage [N, Cs, H/2, W/2] for the k6 s2 p2
     stem (csrc dmy_image_s2d); the result carries `_dmy_s2d` = C, read by ConvBNActFn.  No gradient."""
     N, C, H, W = x.shape
-    Cs = -(-4 * C // VW[dtype]) * VW[dtype]
+    Cs = vec_pad(4 * C, dtype)
     buf = torch.empty((N, Cs, H // 2, W // 2), dtype=dtype, device=x.device, memory_format=CL)
-    xc = x.detach().contiguous()
-    if x.dtype == torch.uint8:
-        call('dmy_image_s2d', DT[dtype], 0, ptr(xc), ptr(buf), N, C, H, W, Cs, 1.0 / 255.0, stream())
-    else:
-        xf = xc if xc.dtype == torch.float32 else xc.float()
-        call('dmy_image_s2d', DT[dtype], 1, ptr(xf), ptr(buf), N, C, H, W, Cs, 1.0, stream())
+    src, kind, scale = _image_src(x.detach())
+    call('dmy_image_s2d', DT[dtype], kind, ptr(src), ptr(buf), N, C, H, W, Cs, scale, stream())
     buf._dmy_s2d = C
     return buf
 
@@ -1246,15 +1252,12 @@ def tta_image(x, dtype, ratio, flip, gs, s2d):
     else:
         OH, OW = int(H * ratio), int(W * ratio)
         OHp, OWp = (math.ceil(v * ratio / gs) * gs for v in (H, W))
-    xc = x.detach().contiguous()
-    kind, scale = (0, 1.0 / 255.0) if x.dtype == torch.uint8 else (1, 1.0)
-    if kind and xc.dtype != torch.float32:
-        xc = xc.float()
+    xc, kind, scale = _image_src(x.detach())
     if s2d:
-        Cs = -(-4 * C // VW[dtype]) * VW[dtype]
+        Cs = vec_pad(4 * C, dtype)
         buf = torch.empty((N, Cs, OHp // 2, OWp // 2), dtype=dtype, device=x.device, memory_format=CL)
     else:
-        Cs = -(-C // VW[dtype]) * VW[dtype]
+        Cs = vec_pad(C, dtype)
         buf = torch.empty((N, Cs, OHp, OWp), dtype=dtype, device=x.device, memory_format=CL)
     call('dmy_tta_image', DT[dtype], kind, ptr(xc), ptr(buf), N, C, H, W, int(bool(s2d)), Cs, scale, flip, OH, OW, OHp,
          OWp, 0.447, stream())
@@ -1273,14 +1276,10 @@ class ToNHWC(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, dtype):
         N, C, H, W = x.shape
-        Cp = -(-C // VW[dtype]) * VW[dtype]
+        Cp = vec_pad(C, dtype)
         buf = torch.empty((N, Cp, H, W), dtype=dtype, device=x.device, memory_format=CL)
-        xc = x.contiguous()
-        if x.dtype == torch.uint8:
-            call('dmy_nchw_to_nhwc', DT[dtype], 0, ptr(xc), ptr(buf), N, C, H, W, Cp, 1.0 / 255.0, stream())
-        else:
-            xf = xc if x.dtype == torch.float32 else xc.float()
-            call('dmy_nchw_to_nhwc', DT[dtype], 1, ptr(xf), ptr(buf), N, C, H, W, Cp, 1.0, stream())
+        src, kind, scale = _image_src(x)  # not detached: forward runs with grad off
+        call('dmy_nchw_to_nhwc', DT[dtype], kind, ptr(src), ptr(buf), N, C, H, W, Cp, scale, stream())
         ctx.src_dtype = x.dtype
         ctx.mark_non_differentiable(buf) if x.dtype == torch.uint8 else None
         return buf[:, :C] if Cp != C else buf

@@ -312,7 +312,7 @@ class Model(nn.Module):
         if x.is_cuda and self._s2d_stem(x):
             return Fn.image_s2d(x, self.act_dtype)
         y = Fn.ToNHWC.apply(x, self.act_dtype)
-        y._dmy_cpad = -(-x.shape[1] // Fn.VW[self.act_dtype]) * Fn.VW[self.act_dtype]  # zero-padded channels
+        y._dmy_cpad = Fn.vec_pad(x.shape[1], self.act_dtype)  # zero-padded channels
         return y
 
     def _weight_prep(self, dev):

@@ -122,3 +122,23 @@ def test_gradient_fanout_plan(cfg, plan):
         n_scconv = sum(2 for layer in m.model if type(layer).__name__ == 'SCConv' and
                        (layer.f if layer.f != -1 else layer.i - 1) == i)
         assert sk.n == aware[i] + n_scconv, (i, sk.n)
+
+
+def test_out_view_rule():
+    """functional.out_view, the output-into-slice rule shared by ConvBNActFn, MaxPoolFn, ResizeFn and maxpool_chain3:
+    a view is written in place only with the result's shape, dtype and device and NHWC-addressable as it stands"""
+    from dmayolo.functional import out_view
+    buf = torch.zeros(2, 32, 4, 4).contiguous(memory_format=torch.channels_last)
+    like = torch.zeros(1)
+    sl = buf[:, 8:24]
+    v, ps = out_view(sl, (2, 16, 4, 4), like)
+    assert v is sl and ps == 32
+    assert out_view(None, (2, 16, 4, 4), like) == (None, None)
+    assert out_view(sl, (2, 16, 4, 2), like) == (None, None)  # wrong shape
+    assert out_view(sl, (2, 16, 4, 4), like.bfloat16()) == (None, None)  # another dtype
+    assert out_view(torch.zeros(2, 32, 4, 4)[:, 8:24], (2, 16, 4, 4), like) == (None, None)  # NCHW-contiguous buffer
+    # a [::2] batch slice: two images twice the image size apart are not addressable in place.  (Out of the batch-2
+    # buffer above the same slice keeps ONE image, which any batch stride addresses: that one is rightly accepted.)
+    buf4 = torch.zeros(4, 32, 4, 4).contiguous(memory_format=torch.channels_last)
+    assert out_view(buf4[::2, 8:24], (2, 16, 4, 4), like) == (None, None)
+    assert out_view(buf[::2, 8:24], (1, 16, 4, 4), like)[1] == 32

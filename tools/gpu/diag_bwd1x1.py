@@ -20,14 +20,16 @@ orig = fn._bwd1x1
 seen = collections.Counter()
 
 
-def wrapped(ctx, dy, dps, x, xps, wt, z, scale, shift, mean, invstd, ca, cb, cc, N, C, H, W, K, k, s, p, M):
-    r = orig(ctx, dy, dps, x, xps, wt, z, scale, shift, mean, invstd, ca, cb, cc, N, C, H, W, K, k, s, p, M)
-    if k == 1 and ctx.train_bn:
+def wrapped(ctx, dy, dps, x, wt, z, stats, coef):
+    r = orig(ctx, dy, dps, x, wt, z, stats, coef)
+    g = ctx.g
+    K, C = g.K, g.C
+    if g.k == 1 and ctx.train_bn:
         why = 'fused' if r is not None else ','.join(n for n, c in (
             ('needs_dx', not ctx.needs_input_grad[0]), ('needs_dw', not ctx.needs_input_grad[1]),
-            ('wt', wt is None), ('s2d', bool(ctx.s2d)), ('cp', ctx.cp != C), ('dtype', dy.dtype != torch.bfloat16),
-            ('stride', s != 1 or p != 0)) if c) or \
-            f'ok-query (K {K} C {C} dps {dps} xps {xps} sink {ctx.xsink is not None})'
+            ('wt', wt is None), ('s2d', bool(g.s2d)), ('cp', g.Cp != C), ('dtype', dy.dtype != torch.bfloat16),
+            ('stride', g.s != 1 or g.p != 0)) if c) or \
+            f'ok-query (K {K} C {C} dps {dps} xps {g.xps} sink {ctx.xsink is not None})'
         seen[(K, C, why)] += 1
     return r
 
