@@ -41,6 +41,15 @@ SIGNATURES = {
     'dmy_conv_wgrad_det': [I, P, P, P, I, I, I, I, L, I, I, I, I, I, I, I, L, I, P, L, P],
     'dmy_conv_route': [I, I, P, P, P, I, I, I, I, L, I, I, I, I, I, I, I, L, I],
     'dmy_conv_wprep': [I, P, P, P, I, I, I, I, I, P],
+    # dwconv.hip
+    'dmy_dwconv_ok': [I, P, P, P, I, I, I, I, I, I, L, I, I, I, I, I, I, L],
+    'dmy_dwconv_fwd_rows': [L, I],
+    'dmy_dwconv_fwd': [I, P, P, P, P, P, P, I, I, I, I, L, I, I, I, I, I, I, L, P],
+    'dmy_dwconv_fwd_act': [I, P, P, P, P, I, I, I, I, L, I, I, I, I, I, I, L, P, P, I, P, L, P],
+    'dmy_dwconv_dgrad': [I, P, P, P, I, I, I, I, I, L, I, I, I, I, I, I, L, P],
+    'dmy_dwconv_wgrad_rows': [L, I],
+    'dmy_dwconv_wgrad': [I, P, P, P, I, I, I, I, L, I, I, I, I, I, I, L, P],
+    'dmy_dwconv_wgrad_finalize': [P, I, I, I, I, P, I, P],
     # bwd1x1.hip
     'dmy_conv1x1_bwd_bn_ok': [L, I, I, L, L, L, P, P, P, P],
     'dmy_conv1x1_bwd_bn': [P, L, P, P, L, P, P, P, P, P, I, P, P, P, P, L, I, P, P, L, L, I, I, P],

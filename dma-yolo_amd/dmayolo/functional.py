@@ -87,12 +87,14 @@ class GradSink:
     the `n` contributions hands the finished buffer to autograd (the others return None).  The
     activation's producer runs only after all of its consumers' backwards, and any contribution
     from outside the module is added by autograd to the finished buffer.  The sink resets after
-    the n-th contribution, so a retained graph can run backward again.
+    the n-th contribution, so a retained graph can run backward again.  adopt=False: a first passthrough contribution
+    is copied into a fresh buffer instead of becoming the buffer, for a gradient that later contributions must not
+    accumulate into (GhostConv: the slice of an upstream gradient that other branches still read).
     """
-    __slots__ = ('n', 'seen', 'buf', 'ps')
+    __slots__ = ('n', 'seen', 'buf', 'ps', 'adopt')
 
-    def __init__(self, n):
-        self.n, self.seen, self.buf, self.ps = n, 0, None, 0
+    def __init__(self, n, adopt=True):
+        self.n, self.seen, self.buf, self.ps, self.adopt = n, 0, None, 0, adopt
 
     def expect(self, k):
         """register k more contributions (a consumer module taking this sink from its caller, in forward)"""
@@ -128,11 +130,14 @@ class GradSink:
         Adoption is safe for the residual pattern: every other reader of g lies inside the branch,
         whose backwards all finish before the branch's first consumer accumulates into g."""
         g, gps = pixel_stride(g)
-        if self.buf is None:
+        if self.buf is None and self.adopt:
             self.buf, self.ps = g, gps
         else:
             N, C, H, W = g.shape
-            call('dmy_slice_copy', dcode(g), ptr(g), gps, ptr(self.buf), self.ps, N * H * W, C, None, 0, 0, 0.0, 1,
+            acc = int(self.buf is not None)
+            if not acc:
+                self.buf, self.ps = new_act(N, C, H, W, g), C
+            call('dmy_slice_copy', dcode(g), ptr(g), gps, ptr(self.buf), self.ps, N * H * W, C, None, 0, 0, 0.0, acc,
                  stream())
         return self._tick()
 
@@ -162,12 +167,13 @@ def set_deterministic(on=True):
     DETERMINISTIC[0] = bool(on)
 
 
-class ConvGeom(namedtuple('ConvGeom', 'N C H W xps K k s p OH OW M Cg Hg Wg kg sg pg Cp s2d')):
+class ConvGeom(namedtuple('ConvGeom', 'N C H W xps K k s p OH OW M Cg Hg Wg kg sg pg Cp s2d groups', defaults=(1,))):
     """Geometry of one conv layer call, built once in ConvBNActFn.forward.  N C H W xps K k s p OH OW (M = N * OH * OW
     output pixels) describe the layer as the model sees it (timer flops and tags, gradient shapes); Cg Hg Wg kg sg pg
     are what the kernels are launched with.  The two differ only for the stem forms: space-to-depth (s2d = Cs, the k6
     s2 p2 conv runs as k3 s1 p1 over Cs channels of the half-size image) and channel-padded (Cp = Cg > C, the
-    zero-padded storage read as 16-byte vectors against zero weights).  Otherwise s2d = 0 and Cp = C."""
+    zero-padded storage read as 16-byte vectors against zero weights).  Otherwise s2d = 0 and Cp = C.  groups is 1 for the
+    dense kernels and C (== K) for a depthwise layer, which runs on the dwconv kernels (csrc/dwconv.hip)."""
     __slots__ = ()
 
     def launch(self):  # the geometry arguments shared by the forward / weight-grad kernels, up to the output size
@@ -177,7 +183,10 @@ class ConvGeom(namedtuple('ConvGeom', 'N C H W xps K k s p OH OW M Cg Hg Wg kg s
         return self.N, self.C, self.H, self.W, self.K, self.k, self.s
 
     def flops(self):
-        return 2.0 * self.M * self.K * self.C * self.k * self.k
+        return 2.0 * self.M * self.K * (self.C // self.groups) * self.k * self.k
+
+    def dw(self):  # the geometry arguments of the depthwise kernels, up to the output size
+        return self.N, self.H, self.W, self.C, self.xps, self.k, self.k, self.s, self.p, self.OH, self.OW
 
 
 def _wgrad(dt, x, dz, dzps, dw, g, flags):
@@ -273,13 +282,15 @@ class WeightPrep:
 class ConvSpec:
     """Static description of one conv(+BN)(+act) layer; `bn` is the live nn.BatchNorm2d (or None).
     wcache / ecache: inference-only caches of the prepped weight and the eval BN coefficients."""
-    __slots__ = ('stride', 'pad', 'act', 'bn', 'wcache', 'ecache', 'fp8', 'f8cache', 'f8_emit', 'defer', '__weakref__')
+    __slots__ = ('stride', 'pad', 'act', 'bn', 'wcache', 'ecache', 'fp8', 'f8cache', 'f8_emit', 'defer', 'groups',
+                 '__weakref__')
 
     def __init__(self, stride, pad, act, bn=None):
         self.stride, self.pad, self.act, self.bn = int(stride), int(pad), int(act), bn
         self.wcache = self.ecache = self.f8cache = self.f8_emit = None
         self.fp8 = False
         self.defer = False  # deferred_affine(): the consumer applies this layer's BN (see SCGateFn)
+        self.groups = 1  # nn.Conv2d.groups of the owning module (spec_for): > 1 selects the depthwise kernels
 
 
 _SPECS = weakref.WeakKeyDictionary()
@@ -292,6 +303,7 @@ def spec_for(owner, stride, pad, act, bn):
     if sp is None or (sp.stride, sp.pad, sp.act) != (int(stride), int(pad), int(act)) or sp.bn is not bn:
         sp = _SPECS[owner] = ConvSpec(stride, pad, act, bn)
     sp.fp8 = bool(getattr(owner, 'dmy_fp8', False))
+    sp.groups = int(getattr(owner, 'groups', 1))
     return sp
 
 
@@ -501,7 +513,10 @@ class KernelTimer:
 def _launch_conv_fwd(x, g, wf, bias, y, yps, psum, psq, epi=None, f8=None):
     """Launch over g's launch geometry; the timer's flops and tag are the layer's real ones (the stem forms differ).
     epi = (scale, shift, act, res, rps): fused inference epilogue (dmy_conv_fwd_act)
-    f8 = (x8, amax, w8, wscale): run on the e4m3 kernel (dmy_conv_fwd_fp8, timer kind conv_fwd_f8)"""
+    f8 = (x8, amax, w8, wscale): run on the e4m3 kernel (dmy_conv_fwd_fp8, timer kind conv_fwd_f8)
+    A depthwise layer (g.groups > 1) goes to _launch_dw_fwd with the same arguments."""
+    if g.groups != 1:
+        return _launch_dw_fwd(x, g, wf, bias, y, yps, psum, psq, epi)
     N, C, H, W, K, k, OH, OW = g.N, g.Cg, g.Hg, g.Wg, g.K, g.kg, g.OH, g.OW
     es, fl, geo = x.element_size(), g.flops(), g.launch()
     kw = dict(tag=g.tag(), nbytes=es * (N * H * W * C + K * C * k * k + N * OH * OW * K))
@@ -525,6 +540,33 @@ def _launch_conv_fwd(x, g, wf, bias, y, yps, psum, psq, epi=None, f8=None):
     else:
         KernelTimer.run('conv_fwd', fl, 'dmy_conv_fwd_act', dt, ptr(x), ptr(wf), ptr(bias), ptr(y), *geo, yps, ptr(sc),
                         ptr(sh), act, ptr(res), rps, stream(), **kw)
+
+
+def _dw_unsupported(groups, C, K, k, s, p):
+    return NotImplementedError(f'grouped conv with groups != channels, or a depthwise geometry the gfx950 kernels do '
+                               f'not take (dmy_dwconv_ok): groups={groups} C={C} K={K} k={k} s={s} p={p}')
+
+
+def _dw_check(dt, a, w, b, g, aps, bps):
+    """dmy_dwconv_ok for the launch about to be made: a / b are the tensors on the input / output side"""
+    if not call('dmy_dwconv_ok', dt, ptr(a), ptr(w), ptr(b), g.N, g.H, g.W, g.C, g.K, g.groups, aps, g.k, g.k, g.s, g.p,
+                g.OH, g.OW, bps):
+        raise _dw_unsupported(g.groups, g.C, g.K, g.k, g.s, g.p)
+
+
+def _launch_dw_fwd(x, g, w, bias, y, yps, psum, psq, epi):
+    """depthwise forward: dmy_dwconv_fwd (training: z and the BN partial rows) or dmy_dwconv_fwd_act (inference
+    epilogue).  w is the [k][k][C] filter operand (the IHWO copy of the (C, 1, k, k) weight)"""
+    dt = dcode(x)
+    _dw_check(dt, x, w, y, g, g.xps, yps)
+    kw = dict(tag=g.tag(), nbytes=x.element_size() * (g.N * g.H * g.W * g.C + g.k * g.k * g.C + g.M * g.C))
+    if epi is None:
+        KernelTimer.run('dwconv_fwd', g.flops(), 'dmy_dwconv_fwd', dt, ptr(x), ptr(w), ptr(bias), ptr(y), ptr(psum),
+                        ptr(psq), *g.dw(), yps, stream(), **kw)
+    else:
+        sc, sh, act, res, rps = epi
+        KernelTimer.run('dwconv_fwd', g.flops(), 'dmy_dwconv_fwd_act', dt, ptr(x), ptr(w), ptr(bias), ptr(y), *g.dw(),
+                        yps, ptr(sc), ptr(sh), act, ptr(res), rps, stream(), **kw)
 
 
 def eval_coef(spec, dev):
@@ -587,6 +629,8 @@ def _conv_operands(x, weight, spec, need_grad, infer):
     wf = spec.wcache[1] if infer and spec.wcache is not None and spec.wcache[0] == wkey else None
     K, C, k, _ = weight.shape
     s, p, wt = spec.stride, spec.pad, None
+    if spec.groups != 1:
+        return _dw_operands(x, weight, spec, need_grad, infer, wkey)
     x, xps = pixel_stride(x)
     if s2d:
         # stem over the space-to-depth image (image_s2d): the k6 s2 p2 conv runs as k3 s1 p1 over Cs channels
@@ -617,10 +661,35 @@ def _conv_operands(x, weight, spec, need_grad, infer):
     return x, g, wf, wt, wkey
 
 
+def _dw_operands(x, weight, spec, need_grad, infer, wkey):
+    """_conv_operands for a depthwise layer (groups == C == K, weight (C, 1, k, k)): the filter operand is [k][k][C] in
+    the activation dtype, which is exactly the IHWO copy the weight prep writes for K = C, C = 1, so forward and
+    data-grad share it (returned as both wf and wt).  Any other grouping has no kernel."""
+    K, one, k, k2 = weight.shape
+    s, p, G = spec.stride, spec.pad, spec.groups
+    if x.dim() != 4 or one != 1 or k != k2 or not (G == K == x.shape[1]) or getattr(x, '_dmy_s2d', 0):
+        raise _dw_unsupported(G, x.shape[1] if x.dim() == 4 else -1, K, k, s, p)
+    x, xps = pixel_stride(x)
+    N, C, H, W = x.shape
+    OH, OW = conv_out_hw(H, W, k, s, p)
+    if OH < 1 or OW < 1 or C % VW[x.dtype] or p != k // 2 or k not in (3, 5) or s not in (1, 2):
+        raise _dw_unsupported(G, C, K, k, s, p)
+    g = ConvGeom(N, C, H, W, xps, K, k, s, p, OH, OW, N * OH * OW, C, H, W, k, s, p, C, 0, G)
+    w = spec.wcache[1] if infer and spec.wcache is not None and spec.wcache[0] == wkey else None
+    pre = WeightPrep.current.get(weight, x.dtype) if WeightPrep.current is not None else None
+    if w is None and pre is not None:
+        w = pre[1]
+    elif w is None:
+        w = prep_weight(weight, x.dtype, True)[1]
+        if infer:
+            spec.wcache = (wkey, w)
+    return x, g, w, w, wkey
+
+
 def _conv_fp8(x, g, weight, spec, wkey, f8in, prod, infer):
     """e4m3 operands (x8, amax, w8, wscale) when the layer runs on the fp8 kernel, else None.  f8in: the e4m3 copy the
     producer emitted with the input (delayed scaling); prod: the producer's spec, asked here to start emitting"""
-    if not (spec.fp8 and not g.s2d and g.Cp == g.C and fp8_eligible(g.C, g.K, x.dtype, g.N * g.H * g.W)):
+    if not (spec.fp8 and g.groups == 1 and not g.s2d and g.Cp == g.C and fp8_eligible(g.C, g.K, x.dtype, g.N * g.H * g.W)):
         return None
     if f8in is not None and (f8in[0].numel() != g.N * g.H * g.W * g.C or not F8_DELAYED[0]):
         f8in = None
@@ -650,11 +719,14 @@ def _conv_bn_stats(x, g, wf, bias, z, bn, train_bn, f8):
         call('dmy_bn_eval_coef', ptr(bn.weight), ptr(bn.bias), ptr(bn.running_mean), ptr(bn.running_var),
              float(bn.eps), K, ptr(scale), ptr(shift), stream())
         return scale, shift, mean, invstd
-    # bf16 / fp32: rows for any route; the launch reports the rows its kernel wrote (halo / LANE: per wave)
-    P = call('dmy_conv_fwd_fp8_partial_rows' if f8 is not None else 'dmy_conv_fwd_bound_rows', M, K)
+    # bf16 / fp32: rows for any route; the launch reports the rows its kernel wrote (halo / LANE: per wave).  A
+    # depthwise launch writes exactly dmy_dwconv_fwd_rows rows
+    dw = g.groups != 1
+    P = call('dmy_dwconv_fwd_rows' if dw else 'dmy_conv_fwd_fp8_partial_rows' if f8 is not None else
+             'dmy_conv_fwd_bound_rows', M, K)
     psum, psq = f32(P * K, dev), f32(P * K, dev)
     _launch_conv_fwd(x, g, wf, bias, z, K, psum, psq, f8=f8)
-    if f8 is None:
+    if f8 is None and not dw:
         P = call('dmy_conv_fwd_last_rows')
     psum, psq, P = _fold_partials(psum, psq, P, K, dev)
     upd = int(bn.training and bn.track_running_stats)
@@ -754,7 +826,7 @@ def _bwd1x1(ctx, dy, dps, x, wt, z, stats, coef):
     in block order instead of fp32 atomics.  stats = (scale, shift, mean, invstd), coef = (ca, cb, cc)."""
     g = ctx.g
     N, C, H, W, xps, K, M = g.N, g.C, g.H, g.W, g.xps, g.K, g.M
-    if not (BWD1X1[0] and ctx.train_bn and g.k == 1 and g.s == 1 and g.p == 0 and not g.s2d and g.Cp == C and
+    if not (BWD1X1[0] and g.groups == 1 and ctx.train_bn and g.k == 1 and g.s == 1 and g.p == 0 and not g.s2d and g.Cp == C and
             dy.dtype == torch.bfloat16 and wt is not None and ctx.needs_input_grad[0] and ctx.needs_input_grad[1]):
         return None
     buf_probe = ctx.xsink.peek(N, C, H, W) if ctx.xsink is not None else None
@@ -801,6 +873,12 @@ def _dgrad(ctx, dt, dz, dzps, wt, z):
     if g.Cp != C or g.s2d:
         raise NotImplementedError('input gradient of a channel-padded stem conv')
     buf, bps, acc = sink_target(ctx.xsink, N, C, H, W, z)
+    if g.groups != 1:  # depthwise: a gather over dz, no atomics
+        _dw_check(dt, buf, wt, dz, g, bps, dzps)
+        KernelTimer.run('dwconv_dgrad', g.flops(), 'dmy_dwconv_dgrad', dt, ptr(dz), ptr(wt), ptr(buf), acc, N, H, W, C,
+                        bps, k, k, g.s, g.p, g.OH, g.OW, dzps, stream(), tag=g.tag(),
+                        nbytes=z.element_size() * (M * C + k * k * C + (1 + acc) * N * H * W * C))
+        return sink_result(ctx.xsink, buf)
     KernelTimer.run('conv_dgrad', g.flops(), 'dmy_conv_dgrad', dt, ptr(dz), ptr(wt), ptr(buf), acc, N, H, W, C, bps, K,
                     k, k, g.s, g.p, g.OH, g.OW, dzps, stream(), tag=g.tag(),
                     nbytes=z.element_size() * (M * K + K * C * k * k + (1 + acc) * N * H * W * C))
@@ -811,6 +889,18 @@ def _conv_wgrad(ctx, dt, x, dz, dzps):
     """the weight gradient in torch OIHW order, in the weight's arena slice when it has one"""
     g = ctx.g
     K, C, k, dev = g.K, g.C, g.k, dz.device
+    if g.groups != 1:
+        # depthwise: per-block partial rows [P][k * k * C], summed in row order into the (C, 1, k, k) gradient (no
+        # atomics: bit-identical run to run with or without set_deterministic)
+        dw, zeroed = _wgrad_target(ctx, (K, 1, k, k), dev)
+        _dw_check(dt, x, dz, dz, g, g.xps, dzps)
+        P = call('dmy_dwconv_wgrad_rows', g.M, C)
+        part = f32(P * k * k * C, dev)
+        KernelTimer.run('dwconv_wgrad', g.flops(), 'dmy_dwconv_wgrad', dt, ptr(x), ptr(dz), ptr(part), *g.dw(), dzps,
+                        stream(), tag=g.tag(),
+                        nbytes=x.element_size() * (g.N * g.H * g.W * C + g.M * C) + 4 * k * k * C)
+        call('dmy_dwconv_wgrad_finalize', ptr(part), P, C, k, k, ptr(dw), int(zeroed), stream())
+        return dw
     dw, zeroed = _wgrad_target(ctx, (K, C, k, k), dev)
     if g.s2d:
         dwo = f32(K * 9 * g.s2d, dev)
@@ -858,7 +948,8 @@ class ConvBNActFn(torch.autograd.Function):
             stats = _conv_bn_stats(x, g, wf, bias, z, bn, train_bn, f8)
             saved = (x, wt, z, *stats, bn.weight)
             if (spec.defer and DEFER_AFFINE[0] and train_bn and need_grad and x.dtype == torch.bfloat16 and
-                    spec.act == ACT_NONE and res is None and out is None and g.K % 8 == 0 and f8 is None):
+                    spec.act == ACT_NONE and res is None and out is None and g.K % 8 == 0 and f8 is None and
+                    g.groups == 1):
                 y, link = z, _defer_affine(z, stats, spec.act, g.K)
             else:
                 y = _act_pass(g, z, stats[0], stats[1], spec, res, rps, out, yps, True)

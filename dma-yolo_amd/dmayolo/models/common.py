@@ -17,7 +17,7 @@ import torch.nn as nn
 from .. import functional as Fn
 from ..functional import ACT_NONE, ACT_SILU, ACT_HARDSWISH, ACT_SIGMOID, ACT_GELU, ACT_RELU
 
-__all__ = ['autopad', 'Conv', 'Bottleneck', 'C3', 'SPPF', 'SPPFCSPC', 'SCConv', 'CoorAttention', 'CA',
+__all__ = ['autopad', 'Conv', 'DWConv', 'GhostConv', 'GhostBottleneck', 'C3Ghost', 'Bottleneck', 'C3', 'SPPF', 'SPPFCSPC', 'SCConv', 'CoorAttention', 'CA',
            'CABottleneck', 'C3CA', 'Concat', 'AdConcat2', 'AdConcat3', 'Upsample', 'C3STR', 'SwinTransformerBlock',
            'SwinTransformerLayer', 'WindowAttention', 'Mlp', 'DropPath', 'space_to_depth', 'SPP', 'CBAM',
            'ChannelAttentionModule', 'SpatialAttentionModule', 'C3TR', 'TransformerBlock', 'TransformerLayer']
@@ -51,10 +51,11 @@ def _pad_int(p):
 
 
 def conv_forward(conv, bn, act, x, res=None, xsink=None, rsink=None, out=None, defer=False):
-    """conv (nn.Conv2d, groups=1, dilation=1) -> optional BN -> act (+ residual) on the HIP path.
+    """conv (nn.Conv2d, dilation=1; groups 1, or depthwise: groups == channels) -> optional BN -> act (+ residual) on
+    the HIP path.  Any other grouping raises NotImplementedError (functional._dw_operands).
     xsink / rsink: Fn.GradSink for the gradients of x / res when they have other consumers.  defer: a train-mode BN
     layer without activation returns its pre-BN output for a consumer that applies the BN itself (SCConv's gate)"""
-    assert conv.groups == 1 and conv.dilation in (1, (1, 1)), 'grouped/dilated conv not on the DMA-YOLO path'
+    assert conv.dilation in (1, (1, 1)), 'dilated conv not on the DMA-YOLO path'
     s = conv.stride if isinstance(conv.stride, int) else conv.stride[0]
     pad, a = _pad_int(conv.padding), act_code(act)
     return Fn.conv_bn_act(x, conv.weight, conv.bias, bn, s, pad, a, res=res, spec=Fn.spec_for(conv, s, pad, a, bn),
@@ -75,6 +76,62 @@ class Conv(nn.Module):
 
     def forward_fuse(self, x, res=None, xsink=None, rsink=None, out=None):
         return conv_forward(self.conv, None, self.act, x, res, xsink, rsink, out)
+
+
+class DWConv(Conv):
+    """Depthwise conv + BN + act, models/common.py:79-82 (groups = gcd(c1, c2); the kernels take c1 == c2)."""
+
+    def __init__(self, c1, c2, k=1, s=1, act=True):
+        super().__init__(c1, c2, k, s, g=math.gcd(c1, c2), act=act)
+
+
+class GhostConv(nn.Module):
+    """Ghost convolution, models/common.py:666-685: cat(y, cv2(y)) with y = cv1(x) and cv2 a 5x5 depthwise conv.
+    One c2-channel NHWC buffer: cv1 writes the first half through out=, cv2 reads that slice (pixel stride c2) and
+    writes the second half, so the concat copies nothing (as C3's in-place concat)."""
+
+    def __init__(self, c1, c2, k=1, s=1, g=1, act=True):
+        super().__init__()
+        c_ = c2 // 2
+        self.cv1 = Conv(c1, c_, k, s, None, g, act)
+        self.cv2 = Conv(c_, c_, 5, 1, None, c_, act)
+
+    def forward(self, x, xsink=None):
+        """xsink: the caller's GradSink for x.  When cv1 has no separate activation pass (a fused linear layer) it
+        returns its own tensor and ConcatFn copies the halves instead."""
+        c_ = self.cv1.conv.out_channels
+        c = self.cv1.conv
+        OH, OW = Fn.conv_out_hw(x.shape[2], x.shape[3], c.kernel_size[0], c.stride[0], c.padding[0])
+        cat = Fn.concat_buffer(x.shape[0], 2 * c_, OH, OW, x)
+        # y -> cv2 and the concat.  The concat's contribution is a slice of the block's upstream gradient, which other
+        # branches (GhostBottleneck's shortcut) still read: cv2's data-grad must not accumulate into it (adopt=False)
+        sk = Fn.GradSink(2, adopt=False)
+        y = self.cv1(x, xsink=xsink, out=cat[:, :c_])
+        return Fn.ConcatFn.apply(None, 0.0, (sk, None), y, self.cv2(y, xsink=sk, out=cat[:, c_:]))
+
+
+class GhostBottleneck(nn.Module):
+    """models/common.py:687-699: conv = GhostConv -> (DWConv when s == 2, else the Identity placeholder) -> GhostConv
+    (linear), plus the shortcut (DWConv -> Conv when s == 2, else identity), added with AddFn."""
+
+    def __init__(self, c1, c2, k=3, s=1):
+        super().__init__()
+        c_ = c2 // 2
+        self.conv = nn.Sequential(GhostConv(c1, c_, 1, 1),
+                                  DWConv(c_, c_, k, s, act=False) if s == 2 else nn.Identity(),
+                                  GhostConv(c_, c2, 1, 1, act=False))
+        self.shortcut = nn.Sequential(DWConv(c1, c1, k, s, act=False),
+                                      Conv(c1, c2, 1, 1, act=False)) if s == 2 else nn.Identity()
+
+    def forward(self, x):
+        sk = Fn.GradSink(2)  # x -> conv[0].cv1 and the shortcut
+        a = self.conv[0](x, xsink=sk)
+        if not isinstance(self.conv[1], nn.Identity):
+            a = self.conv[1](a)
+        a = self.conv[2](a)
+        if isinstance(self.shortcut, nn.Identity):
+            return Fn.AddFn.apply(x, a, sk)
+        return Fn.AddFn.apply(self.shortcut[1](self.shortcut[0](x, xsink=sk)), a, None)
 
 
 class Bottleneck(nn.Module):
@@ -181,6 +238,15 @@ class C3(nn.Module):
         else:
             a = self.m(a, out=cat[:, :c_])
         return self.cv3(Fn.ConcatFn.apply(None, 0.0, None, a, self.cv2(x, xsink=sk, out=cat[:, c_:])), out=out)
+
+
+class C3Ghost(C3):
+    """models/common.py:205-210: C3 whose bottleneck stack is n GhostBottleneck(c_, c_)."""
+
+    def __init__(self, c1, c2, n=1, shortcut=True, g=1, e=0.5):
+        super().__init__(c1, c2, n, shortcut, g, e)
+        c_ = int(c2 * e)
+        self.m = nn.Sequential(*(GhostBottleneck(c_, c_) for _ in range(n)))
 
 
 class SPPF(nn.Module):

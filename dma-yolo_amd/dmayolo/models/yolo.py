@@ -20,7 +20,7 @@ import torch.nn as nn
 from .. import functional as Fn
 from ..functional import call, ptr, stream, dcode
 from .common import *  # noqa: F401,F403  (the YAML namespace)
-from .common import Conv, Upsample, SCConv, autopad, space_to_depth
+from .common import Conv, Upsample, SCConv, GhostConv, GhostBottleneck, autopad, space_to_depth
 from .tdetect import TDetect
 from ..utils.general import make_divisible
 from ..utils.torch_utils import initialize_weights, fuse_conv_and_bn
@@ -115,10 +115,12 @@ def _out_hw(m, hw):
         for mm in m:
             hw = _out_hw(mm, hw)
         return hw
-    if isinstance(m, Conv):
-        c = m.conv
+    if isinstance(m, (Conv, GhostConv)):  # DWConv is a Conv; GhostConv's map is its cv1's (cv2 is k5 s1 p2)
+        c = m.conv if isinstance(m, Conv) else m.cv1.conv
         k, s, p = c.kernel_size[0], c.stride[0], c.padding[0]
         return ((hw[0] + 2 * p - k) // s + 1, (hw[1] + 2 * p - k) // s + 1)
+    if isinstance(m, GhostBottleneck):
+        return _out_hw(m.conv[1], hw)  # the stride-2 DWConv, or the Identity placeholder
     if isinstance(m, SCConv):
         s = m.k4[0].stride[0]
         return ((hw[0] - 1) // s + 1, (hw[1] - 1) // s + 1)
@@ -316,14 +318,15 @@ class Model(nn.Module):
         return y
 
     def _weight_prep(self, dev):
-        """functional.WeightPrep over every groups-1 Conv2d except a 3-channel stem (space-to-depth /
+        """functional.WeightPrep over every groups-1 or depthwise Conv2d except a 3-channel stem (space-to-depth /
         channel-padded, prepped by its own layout kernel); rebuilt when the parameters move or fuse() ran"""
         first = next(self.parameters())
         key = (first.data_ptr(), dev, self.act_dtype)
         c = getattr(self, '_prep', None)
         if c is None or c[0] != key:
-            ws = [m.weight for m in self.modules() if isinstance(m, nn.Conv2d) and m.groups == 1 and
-                  m.in_channels > 4 and m.dilation in (1, (1, 1)) and m.weight.requires_grad]
+            ws = [m.weight for m in self.modules() if isinstance(m, nn.Conv2d) and
+                  (m.groups == 1 or m.groups == m.in_channels == m.out_channels) and m.in_channels > 4 and
+                  m.dilation in (1, (1, 1)) and m.weight.requires_grad]
             c = self._prep = (key, Fn.WeightPrep(ws, self.act_dtype, dev))
         return c[1]
 
@@ -510,9 +513,9 @@ def parse_model(d, ch):
     na = (len(anchors[0]) // 2) if isinstance(anchors, list) else anchors
     no = na * (nc + 5)
     ev = dict(ns, nc=nc, anchors=anchors)
-    chan_mods = (C.Conv, C.Bottleneck, C.SPPF, C.C3, C.C3TR, C.C3STR, C.CoorAttention, C.CABottleneck, C.C3CA,
+    chan_mods = (C.Conv, C.DWConv, C.GhostConv, C.GhostBottleneck, C.C3Ghost, C.Bottleneck, C.SPPF, C.C3, C.C3TR, C.C3STR, C.CoorAttention, C.CABottleneck, C.C3CA,
                  C.SPPFCSPC, C.SCConv, C.SPP, C.CBAM)
-    rep_mods = (C.C3, C.C3TR, C.C3STR, C.C3CA)
+    rep_mods = (C.C3, C.C3TR, C.C3STR, C.C3CA, C.C3Ghost)
     layers, save, c2 = [], [], ch[-1]
     for i, (f, n, m, args) in enumerate(d['backbone'] + d['head']):
         m = eval(m, ev) if isinstance(m, str) else m

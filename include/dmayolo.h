@@ -135,6 +135,41 @@ int dmy_conv_wprep_s2d(int dtype, const float* w_oihw, void* w_s2d, int K, int C
 int dmy_conv_wgrad_s2d_to_oihw(const float* dw_s2d, float* dw_oihw, int K, int C, int Cs, void* stream);
 int dmy_conv_wgrad_to_oihw(const float* dw_ohwi, float* dw_oihw, int K, int C, int Cp, int KH, int KW, void* stream);
 
+/* ---- depthwise convolution (csrc/dwconv.hip): replaces nn.Conv2d(c, c, k, s, k // 2, groups=c) in DWConv
+ *      (models/common.py:79-82) and GhostConv.cv2 (:666-699).  One k x k filter per channel, no reduction over
+ *      channels: streaming kernels over NHWC, fp32 accumulation, no atomics (run-to-run bit-identical).
+ *      w is the filter tap-major, channel-minor [KH][KW][C] in the activation dtype: exactly the IHWO copy
+ *      dmy_conv_wprep / dmy_conv_wprep_multi write for a (C, 1, k, k) OIHW weight (K = C, C = 1).
+ *      dmy_dwconv_ok (models/common.py:79-82): 1 when the layer is supported -- groups == C == K, square k in
+ *      {3, 5}, stride 1 or 2, padding k / 2, OH / OW the conv's output size, C a whole number of 16-byte vectors
+ *      (C % 8 bf16, C % 4 fp32), pixel strides >= C and whole vectors, 16-byte aligned bases.  Every other entry
+ *      returns -1 and launches nothing when its arguments fail that test. */
+int dmy_dwconv_ok(int dtype, const void* x, const void* w, const void* z, int N, int H, int W, int C, int K, int groups,
+                  long xps, int KH, int KW, int S, int P, int OH, int OW, long zps);
+/* models/common.py:79-82 in training: z = T(conv + bias) (bias nullable).  psum / psq (nullable together): per-block
+ * partial sums and sums of squares of the values as stored, dmy_dwconv_fwd_rows(M = N * OH * OW, C) rows of C floats,
+ * every row written; they feed dmy_colsum2 / dmy_bn_finalize like dmy_conv_fwd's. */
+int dmy_dwconv_fwd_rows(long M, int C);
+int dmy_dwconv_fwd(int dtype, const void* x, const void* w, const float* bias, void* z, float* psum, float* psq, int N,
+                   int H, int W, int C, long xps, int KH, int KW, int S, int P, int OH, int OW, long zps, void* stream);
+/* models/common.py:79-82 in inference (eval BN / fused DWConv), one launch with dmy_conv_fwd_act's semantics:
+ * y = act(T(conv + bias) * scale + shift) (+ res); scale / shift nullable together. */
+int dmy_dwconv_fwd_act(int dtype, const void* x, const void* w, const float* bias, void* y, int N, int H, int W, int C,
+                       long xps, int KH, int KW, int S, int P, int OH, int OW, long yps, const float* scale,
+                       const float* shift, int act, const void* res, long rps, void* stream);
+/* backward of models/common.py:79-82 w.r.t. its input, as a gather: each dx element sums the taps (i, j) whose
+ * (h + P - i) and (w + P - j) are divisible by S.  accumulate as in dmy_conv_dgrad (dx += for GradSink targets). */
+int dmy_dwconv_dgrad(int dtype, const void* dz, const void* w, void* dx, int accumulate, int N, int H, int W, int C,
+                     long xps, int KH, int KW, int S, int P, int OH, int OW, long zps, void* stream);
+/* backward of models/common.py:79-82 w.r.t. its weight: dmy_dwconv_wgrad writes dmy_dwconv_wgrad_rows(M, C) partial
+ * rows [KH * KW * C] (tap-major), dmy_dwconv_wgrad_finalize sums them in row order into the (C, 1, KH, KW) OIHW fp32
+ * gradient: dw = (accumulate ? dw : 0) + sum. */
+int dmy_dwconv_wgrad_rows(long M, int C);
+int dmy_dwconv_wgrad(int dtype, const void* x, const void* dz, float* part, int N, int H, int W, int C, long xps, int KH,
+                     int KW, int S, int P, int OH, int OW, long zps, void* stream);
+int dmy_dwconv_wgrad_finalize(const float* part, int rows, int C, int KH, int KW, float* dw, int accumulate,
+                              void* stream);
+
 /* ---- fp8 (OCP e4m3fn) forward conv for config 5 (BASELINE configs[4], "fp8 MFMA conv"): replaces the forward of
  *      Conv.conv (models/common.py:61-74) when enabled; backward stays bf16.  Activations are quantised per
  *      tensor with the current amax (x ~ x8 * amax / 448), weights per output channel (w ~ w8 * wscale[k]);
