@@ -70,7 +70,8 @@ template <int N> DEV void ldf(const float* p, float* o) {
 }
 
 // Activation codes shared with the host (dmayolo/_lib.py ACT_*).
-enum Act : int { ACT_NONE = 0, ACT_SILU = 1, ACT_HARDSWISH = 2, ACT_SIGMOID = 3, ACT_GELU = 4, ACT_RELU = 5 };
+// ACT_LEAKY is nn.LeakyReLU(0.1), the slope add_conv fixes (models/common.py:1063-1081).
+enum Act : int { ACT_NONE = 0, ACT_SILU = 1, ACT_HARDSWISH = 2, ACT_SIGMOID = 3, ACT_GELU = 4, ACT_RELU = 5, ACT_LEAKY = 6 };
 
 DEV float act_fwd(int act, float u) {
   switch (act) {
@@ -79,6 +80,7 @@ DEV float act_fwd(int act, float u) {
     case ACT_SIGMOID: return sigmoidf_(u);
     case ACT_GELU: return 0.5f * u * (1.0f + erff(u * 0.70710678118654752f));
     case ACT_RELU: return fmaxf(u, 0.0f);
+    case ACT_LEAKY: return u > 0.0f ? u : 0.1f * u;
     default: return u;
   }
 }
@@ -94,6 +96,10 @@ template <int N> DEV void act_fwd_n(int act, float* u) {
     case ACT_RELU:
 #pragma unroll
       for (int e = 0; e < N; ++e) u[e] = fmaxf(u[e], 0.0f);
+      break;
+    case ACT_LEAKY:
+#pragma unroll
+      for (int e = 0; e < N; ++e) u[e] = u[e] > 0.0f ? u[e] : 0.1f * u[e];
       break;
     case ACT_NONE: break;
     default:
@@ -115,6 +121,7 @@ DEV float act_grad(int act, float u) {
       return s * (1.0f - s);
     }
     case ACT_RELU: return u > 0.0f ? 1.0f : 0.0f;  // torch threshold_backward (result > 0)
+    case ACT_LEAKY: return u > 0.0f ? 1.0f : 0.1f;  // torch leaky_relu_backward
     case ACT_GELU: {
       const float kA = 0.70710678118654752f, kB = 0.3989422804014327f;  // 1/sqrt2, 1/sqrt(2pi)
       return 0.5f * (1.0f + erff(u * kA)) + u * kB * expf(-0.5f * u * u);
@@ -135,6 +142,10 @@ template <int N> DEV void act_grad_n(int act, float* u) {
     case ACT_RELU:
 #pragma unroll
       for (int e = 0; e < N; ++e) u[e] = u[e] > 0.0f ? 1.0f : 0.0f;
+      break;
+    case ACT_LEAKY:
+#pragma unroll
+      for (int e = 0; e < N; ++e) u[e] = u[e] > 0.0f ? 1.0f : 0.1f;
       break;
     case ACT_NONE:
 #pragma unroll

@@ -50,6 +50,12 @@ SIGNATURES = {
     'dmy_dwconv_wgrad_rows': [L, I],
     'dmy_dwconv_wgrad': [I, P, P, P, I, I, I, I, L, I, I, I, I, I, I, L, P],
     'dmy_dwconv_wgrad_finalize': [P, I, I, I, I, P, I, P],
+    # adapt.hip
+    'dmy_adapt_gate_blocks': [I, L, I, I],
+    'dmy_adapt_gate_fwd': [I, I, P, L, I, P, L, I, P, L, I, P, L, P, P, P, L, P, L, P],
+    'dmy_adapt_gate_bwd': [I, I, P, L, P, L, I, P, L, I, P, L, I, P, P, L, P, P, L, P, L, P, L, I, P, L, P, P, L, P],
+    'dmy_adapt_add_fwd': [I, I, P, L, P, L, P, L, P, F, P, L, L, I, P],
+    'dmy_adapt_add_bwd': [I, I, P, L, P, L, P, L, P, L, P, F, P, L, P, L, P, L, I, P, L, I, P],
     # bwd1x1.hip
     'dmy_conv1x1_bwd_bn_ok': [L, I, I, L, L, L, P, P, P, P],
     'dmy_conv1x1_bwd_bn': [P, L, P, P, L, P, P, P, P, P, I, P, P, P, P, L, I, P, P, L, L, I, I, P],
@@ -222,4 +228,4 @@ def ptr(t):
     return None if t is None else ctypes.c_void_p(t.data_ptr())
 
 
-ACT_NONE, ACT_SILU, ACT_HARDSWISH, ACT_SIGMOID, ACT_GELU, ACT_RELU = 0, 1, 2, 3, 4, 5
+ACT_NONE, ACT_SILU, ACT_HARDSWISH, ACT_SIGMOID, ACT_GELU, ACT_RELU, ACT_LEAKY = 0, 1, 2, 3, 4, 5, 6

@@ -15,10 +15,11 @@ import torch
 import torch.nn as nn
 
 from .. import functional as Fn
-from ..functional import ACT_NONE, ACT_SILU, ACT_HARDSWISH, ACT_SIGMOID, ACT_GELU, ACT_RELU
+from ..functional import ACT_NONE, ACT_SILU, ACT_HARDSWISH, ACT_SIGMOID, ACT_GELU, ACT_RELU, ACT_LEAKY
 
 __all__ = ['autopad', 'Conv', 'DWConv', 'GhostConv', 'GhostBottleneck', 'C3Ghost', 'Bottleneck', 'C3', 'SPPF', 'SPPFCSPC', 'SCConv', 'CoorAttention', 'CA',
-           'CABottleneck', 'C3CA', 'Concat', 'AdConcat2', 'AdConcat3', 'Upsample', 'C3STR', 'SwinTransformerBlock',
+           'CABottleneck', 'C3CA', 'Concat', 'AdConcat2', 'AdConcat3', 'AdaptConcat', 'Adapt_Add2', 'Adapt_Add3', 'AdaptADD',
+           'Upsample', 'C3STR', 'SwinTransformerBlock',
            'SwinTransformerLayer', 'WindowAttention', 'Mlp', 'DropPath', 'space_to_depth', 'SPP', 'CBAM',
            'ChannelAttentionModule', 'SpatialAttentionModule', 'C3TR', 'TransformerBlock', 'TransformerLayer']
 
@@ -43,6 +44,11 @@ def act_code(m):
         return ACT_GELU
     if isinstance(m, nn.ReLU):
         return ACT_RELU
+    if isinstance(m, nn.LeakyReLU):
+        if m.negative_slope != 0.1:
+            raise NotImplementedError(f'LeakyReLU({m.negative_slope}) has no gfx950 kernel (only the slope 0.1 of '
+                                      'add_conv, models/common.py:1080)')
+        return ACT_LEAKY
     raise NotImplementedError(f'activation {type(m).__name__} has no gfx950 kernel')
 
 
@@ -522,6 +528,102 @@ class space_to_depth(nn.Module):
 
     def forward(self, x):
         return Fn.SpaceToDepthFn.apply(x)
+
+
+class _AddConv(nn.Sequential):
+    """add_conv's stage, models/common.py:1063-1081: conv (no bias) -> batch_norm -> LeakyReLU(0.1), with the
+    reference's child names.  Model.fuse() leaves its BN alone, as the reference does (it fuses Conv / DWConv only)."""
+
+    def forward(self, x, xsink=None, out=None):
+        return conv_forward(self.conv, self.batch_norm, self.leaky, x, xsink=xsink, out=out)
+
+
+def add_conv(in_ch, out_ch, ksize=1, stride=1):
+    """models/common.py:1063-1081."""
+    stage = _AddConv()
+    stage.add_module('conv', nn.Conv2d(in_ch, out_ch, ksize, stride, (ksize - 1) // 2, bias=False))
+    stage.add_module('batch_norm', nn.BatchNorm2d(out_ch))
+    stage.add_module('leaky', nn.LeakyReLU(0.1))
+    return stage
+
+
+def _fan(sinks, i, k):
+    """input i's GradSink with k more contributions registered: the caller's, or a fresh one for k > 1"""
+    sk = sinks[i] if sinks is not None else None
+    if sk is not None:
+        return sk.expect(k)
+    return Fn.GradSink(k) if k > 1 else None
+
+
+class AdaptConcat(nn.Module):
+    """Concat with per-pixel learned weights, models/common.py:953-992: each input's add_conv gives 16 level-map
+    channels, weight_levels (a 1x1 conv with bias) turns them into one logit per input, and the inputs are scaled by the
+    softmax of the logits before the concat.  The add_conv stages write their maps side by side into one buffer and one
+    kernel does weight_levels, the softmax, the scaling and the concat (Fn.AdaptGateFn).  A level-2 module keeps the
+    reference's weight_map2 (dim3 = 1), which no forward uses."""
+
+    def __init__(self, level, dimension, dim1, dim2, dim3=1, rfb=False):
+        super().__init__()
+        self.level, self.d, self.dims = level, dimension, [dim1, dim2, dim3]
+        compress_c = 8 if rfb else 16
+        self.weight_map0 = add_conv(self.dims[0], compress_c, 1, 1)
+        self.weight_map1 = add_conv(self.dims[1], compress_c, 1, 1)
+        self.weight_map2 = add_conv(self.dims[2], compress_c, 1, 1)
+        self.weight_levels = nn.Conv2d(compress_c * level, level, kernel_size=1, stride=1, padding=0)
+
+    def forward(self, x, sinks=None):
+        """sinks: None or one GradSink-or-None per input (Model fan-out); each input has two consumers here, its
+        add_conv and the gate, which accumulate into one buffer"""
+        L = self.level
+        assert self.d == 1 and L in (2, 3) and len(x) == L
+        cc = self.weight_map0.conv.out_channels
+        N, _, H, W = x[0].shape
+        sks = [_fan(sinks, i, 2) for i in range(L)]
+        wm = Fn.concat_buffer(N, cc * L, H, W, x[0])
+        maps = [getattr(self, f'weight_map{i}')(x[i], xsink=sks[i], out=wm[:, cc * i:cc * (i + 1)]) for i in range(L)]
+        wm = Fn.ConcatFn.apply(None, 0.0, None, *maps)
+        return Fn.AdaptGateFn.apply(self.weight_levels.weight, self.weight_levels.bias, tuple(sks), wm, *x)
+
+
+class Adapt_Add2(nn.Module):
+    """models/common.py:1028-1044: silu(w0' x0 + w1' x1), w' = w / (sum w + 1e-4)."""
+
+    def __init__(self):
+        super().__init__()
+        self.w = nn.Parameter(torch.ones(2, dtype=torch.float32), requires_grad=True)
+        self.epsilon = 0.0001
+        self.silu = nn.SiLU()
+
+    def forward(self, x, sinks=None):
+        assert len(x) == 2
+        return Fn.AdaptAddFn.apply(self.w, self.epsilon, _join(sinks), *x)
+
+
+class Adapt_Add3(nn.Module):
+    """models/common.py:1046-1061: silu(w0' conv(x0) + w1' conv(x1) + w2' x2), one 1x1 conv (bias, no BN, no activation)
+    applied to both x0 and x1."""
+
+    def __init__(self, d1, d2, d3):
+        super().__init__()
+        self.w = nn.Parameter(torch.ones(3, dtype=torch.float32), requires_grad=True)
+        self.epsilon = 0.0001
+        self.conv = nn.Conv2d(d1, d3, kernel_size=1, stride=1, padding=0)
+        self.silu = nn.SiLU()
+
+    def forward(self, x, sinks=None):
+        assert len(x) == 3
+        a = conv_forward(self.conv, None, None, x[0], xsink=_fan(sinks, 0, 1))
+        b = conv_forward(self.conv, None, None, x[1], xsink=_fan(sinks, 1, 1))
+        return Fn.AdaptAddFn.apply(self.w, self.epsilon, (None, None, _fan(sinks, 2, 1)), a, b, x[2])
+
+
+class AdaptADD(nn.Module):
+    """models/common.py:912-951 does not construct in the reference itself (its __init__ lacks an argument that
+    parse_model passes); not provided."""
+
+    def __init__(self, *args, **kwargs):
+        raise NotImplementedError('AdaptADD (adaptadd.yaml) does not build in the reference and is not provided; '
+                                  'use AdaptConcat or Adapt_Add2 / Adapt_Add3')
 
 
 class Upsample(nn.Upsample):

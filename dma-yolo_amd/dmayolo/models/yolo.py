@@ -424,8 +424,8 @@ class Model(nn.Module):
     # profiles/r04/model_sinks_ab.log) put it within the +-0.5 % run-to-run noise -- DMA-1536 +0.35 % with Detect
     # included, -0.3 %..+0.05 % without; yolov5s -0.3 % with Detect (its only multi-consumer outputs are read by a Conv
     # and Detect, whose narrow-K data-grad then accumulates), so Detect joins only under DMY_SINK_DETECT=1.
-    _SINK_TYPES = ('Conv', 'SCConv', 'AdConcat2', 'AdConcat3') + (('Detect',) if os.environ.get('DMY_SINK_DETECT') == '1'
-                                                                  else ())
+    _SINK_TYPES = ('Conv', 'SCConv', 'AdConcat2', 'AdConcat3', 'AdaptConcat', 'Adapt_Add2', 'Adapt_Add3') + \
+        (('Detect',) if os.environ.get('DMY_SINK_DETECT') == '1' else ())
 
     def _fanout(self):
         """{layer index: consumer count} for outputs read by >= 2 layers, >= 1 of them sink-aware (cached)"""
@@ -537,6 +537,11 @@ def parse_model(d, ch):
             args = [ch[f]]
         elif m in (C.Concat, C.AdConcat2, C.AdConcat3):
             c2 = sum(ch[x] for x in f)
+        elif m in (C.AdaptConcat, C.AdaptADD):  # models/yolo.py:415-419
+            c2 = sum(ch[x] for x in f)
+            args = [len(f), *args]
+        elif m in (C.Adapt_Add2, C.Adapt_Add3):  # models/yolo.py:420-421
+            c2 = max(ch[x] for x in f)
         elif m is Detect:
             args.append([ch[x] for x in f])
             if isinstance(args[1], int):

@@ -261,10 +261,10 @@ def ema_update(ema_tensors, model_tensors, d):
 
 
 def param_groups(model):
-    """train.py:197-214 grouping: g0 BN weights (no decay), g1 weights + AdConcat.w (decay), g2 biases.
+    """train.py:197-214 grouping: g0 BN weights (no decay), g1 weights + AdConcat.w / Adapt_Add.w (decay), g2 biases.
     (relative_position_bias_table and other non-weight/bias params are NOT collected, as in the reference.)"""
     import torch.nn as nn
-    from .models.common import AdConcat2, AdConcat3
+    from .models.common import AdConcat2, AdConcat3, Adapt_Add2, Adapt_Add3
     g0, g1, g2 = [], [], []
     for v in model.modules():
         if hasattr(v, 'bias') and isinstance(v.bias, nn.Parameter):
@@ -273,7 +273,7 @@ def param_groups(model):
             g0.append(v.weight)
         elif hasattr(v, 'weight') and isinstance(v.weight, nn.Parameter):
             g1.append(v.weight)
-        elif isinstance(v, (AdConcat2, AdConcat3)) and isinstance(v.w, nn.Parameter):
+        elif isinstance(v, (AdConcat2, AdConcat3, Adapt_Add2, Adapt_Add3)) and isinstance(v.w, nn.Parameter):
             g1.append(v.w)
     return g0, g1, g2
 

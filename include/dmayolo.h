@@ -170,6 +170,37 @@ int dmy_dwconv_wgrad(int dtype, const void* x, const void* dz, float* part, int 
 int dmy_dwconv_wgrad_finalize(const float* part, int rows, int C, int KH, int KW, float* dw, int accumulate,
                               void* stream);
 
+/* ---- adaptive-fusion necks (csrc/adapt.hip): AdaptConcat (models/common.py:953-992) and Adapt_Add2 / Adapt_Add3
+ *      (models/common.py:1028-1061).  Streaming NHWC kernels, fp32 arithmetic, no atomics (run-to-run bit-identical).
+ *      Every tensor has its own pixel stride.  Supported: bf16 with every channel count and stride a multiple of 8,
+ *      fp32 a multiple of 4, 16-byte aligned bases; anything else returns -1 and launches nothing.
+ *      Gate (models/common.py:979-990), L = 2 or 3 levels (x2 / C2 ignored for L = 2): wm [M][16 L] are the level maps
+ *      the three add_conv blocks (:1063-1081) wrote side by side, W [L][16 L] / b [L] the weight_levels conv (:966) in
+ *      fp32.  Per pixel: a = softmax(W wm + b) in fp32 with the maximum subtracted, y[:, off_l : off_l + C_l] =
+ *      x_l * a_l rounded once to storage; a [M][L] fp32 is kept for the backward. */
+int dmy_adapt_gate_blocks(int dtype, long M, int Ct, int L);
+int dmy_adapt_gate_fwd(int dtype, int L, const void* x0, long x0ps, int C0, const void* x1, long x1ps, int C1,
+                       const void* x2, long x2ps, int C2, const void* wm, long wmps, const float* W, const float* b,
+                       void* y, long yps, float* a, long M, void* stream);
+/* backward of models/common.py:979-990.  Per pixel da_l = sum_c dy_{l,c} x_{l,c}, dlogit = a * (da - sum a da);
+ * dx_l = dy_l * a_l (bit l of accumulate: dx_l += for a GradSink target), dwm = W^T dlogit, and one partial row per
+ * block, dmy_adapt_gate_blocks(dtype, M, Ct = sum C_l, L) rows, every row written: pdw [rows][L * 16 L] of
+ * sum_m dlogit (x) wm and pdb [rows][L] of sum_m dlogit, for dmy_reduce_rows. */
+int dmy_adapt_gate_bwd(int dtype, int L, const void* dy, long dps, const void* x0, long x0ps, int C0, const void* x1,
+                       long x1ps, int C1, const void* x2, long x2ps, int C2, const float* a, const void* wm, long wmps,
+                       const float* W, void* dx0, long dx0ps, void* dx1, long dx1ps, void* dx2, long dx2ps,
+                       int accumulate, void* dwm, long dwmps, float* pdw, float* pdb, long M, void* stream);
+/* models/common.py:1040-1044 (n = 2) and :1057-1061 (n = 3, after the shared 1x1 conv): y = silu(sum_i wn_i x_i) with
+ * wn = w / (sum w + eps) computed on the device; the n inputs have C channels each (x2 ignored for n = 2). */
+int dmy_adapt_add_fwd(int dtype, int n, const void* x0, long x0ps, const void* x1, long x1ps, const void* x2, long x2ps,
+                      const float* w, float eps, void* y, long yps, long M, int C, void* stream);
+/* backward of the above: s is recomputed from the inputs, dx_i = wn_i dy silu'(s) (bit i of accumulate: dx_i +=), and
+ * part [n][dmy_dot_partial_blocks(M, C)] holds the per-block shares of sum dy silu'(s) x_i, which dmy_bifpn_wgrad
+ * turns into dw (the normalisation is AdConcat's). */
+int dmy_adapt_add_bwd(int dtype, int n, const void* dy, long dps, const void* x0, long x0ps, const void* x1, long x1ps,
+                      const void* x2, long x2ps, const float* w, float eps, void* dx0, long dx0ps, void* dx1, long dx1ps,
+                      void* dx2, long dx2ps, int accumulate, float* part, long M, int C, void* stream);
+
 /* ---- fp8 (OCP e4m3fn) forward conv for config 5 (BASELINE configs[4], "fp8 MFMA conv"): replaces the forward of
  *      Conv.conv (models/common.py:61-74) when enabled; backward stays bf16.  Activations are quantised per
  *      tensor with the current amax (x ~ x8 * amax / 448), weights per output channel (w ~ w8 * wscale[k]);
