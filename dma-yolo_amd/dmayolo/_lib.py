@@ -86,6 +86,15 @@ SIGNATURES = {
     'dmy_bn_reduce_rows': [I, P, L, P, L, L, I],
     'dmy_colsum2_rows': [L],
     'dmy_colsum2': [P, P, L, I, P, P, P],
+    # spd.hip
+    'dmy_bn_act_s2d_fwd': [I, P, L, P, P, I, P, L, I, I, I, I, P],
+    'dmy_bn_bwd_reduce_s2d_rows': [I, L, I],
+    'dmy_bn_bwd_reduce_s2d': [I, P, L, P, L, P, P, P, P, I, I, I, I, I, P, P, P],
+    'dmy_bn_bwd_apply_s2d': [I, P, L, P, L, P, P, P, P, I, P, P, P, P, L, I, I, I, I, P],
+    'dmy_maxpool2_fwd': [I, P, L, P, L, P, I, I, I, I, P],
+    'dmy_maxpool2_bwd': [I, P, L, P, P, L, I, I, I, I, I, P],
+    'dmy_spd_split_fwd': [I, P, L, P, L, P, L, P, I, I, I, I, P],
+    'dmy_spd_split_bwd': [I, P, L, P, L, P, P, L, I, I, I, I, P],
     # eltwise.hip
     'dmy_maxpool_fwd': [I, P, L, P, L, P, I, I, I, I, I, P],
     'dmy_maxpool_chain3_fwd': [I, P, L, P, P, P, L, I, I, I, I, I, P],

@@ -699,6 +699,33 @@ def _conv_fp8(x, g, weight, spec, wkey, f8in, prod, infer):
     return f8
 
 
+def even_hw(H, W, what):
+    """SM folds 2 x 2 pixels into channels: an odd map has no SM layout (the reference's cat fails on it too)"""
+    if H < 2 or W < 2 or H % 2 or W % 2:
+        raise ValueError(f'{what} needs a map with even height and width (SM folds 2 x 2 pixels into channels, '
+                         f'models/common.py:1467), got {H}x{W}')
+
+
+def _spd_shape(g, x, res):
+    """output shape of an spd layer (N, 4K, OH / 2, OW / 2), after checking that the SM passes take it"""
+    even_hw(g.OH, g.OW, 'a conv followed by SM')
+    if res is not None:
+        raise NotImplementedError('an spd conv layer takes no residual')
+    if g.K % VW[x.dtype] or g.K // VW[x.dtype] > 256:
+        raise NotImplementedError(f'the SM passes (csrc/spd.hip) take whole 16-byte vectors, at most 256 per pixel: '
+                                  f'output channels multiples of {VW[x.dtype]} for {x.dtype}, got {g.K}')
+    return g.N, 4 * g.K, g.OH // 2, g.OW // 2
+
+
+def _conv_infer_spd(x, g, wf, bias, spec, out, yps, f8):
+    """inference of an spd layer: the one-launch conv into a temporary, then dmy_space_to_depth into the destination
+    (folding SM into the conv epilogue is the follow-up)"""
+    t = _conv_infer(x, g, wf, bias, spec, None, 0, None, g.K, f8)
+    y = out if out is not None else new_act(g.N, 4 * g.K, g.OH // 2, g.OW // 2, x)
+    call('dmy_space_to_depth', dcode(x), ptr(t), g.K, ptr(y), yps, g.N, g.OH, g.OW, g.K, 0, stream())
+    return y
+
+
 def _conv_infer(x, g, wf, bias, spec, res, rps, out, yps, f8):
     """one fused launch: conv + eval-BN + act (+ residual)"""
     y = out if out is not None else new_act(g.N, g.K, g.OH, g.OW, x)
@@ -751,10 +778,16 @@ def _defer_affine(z, stats, act, K):
     return link
 
 
-def _act_pass(g, z, scale, shift, spec, res, rps, out, yps, emit_ok):
+def _act_pass(g, z, scale, shift, spec, res, rps, out, yps, emit_ok, spd=False):
     """The activation pass y = act(z * scale + shift) (+ residual), into `out` when given.  emit_ok (a BN layer): when
-    an fp8 consumer asked for it (spec.f8_emit), the pass also emits the e4m3 copy of y, attached as `_dmy_f8`."""
+    an fp8 consumer asked for it (spec.f8_emit), the pass also emits the e4m3 copy of y, attached as `_dmy_f8`.
+    spd: the pass stores y in SM layout, (N, 4K, OH / 2, OW / 2) (dmy_bn_act_s2d_fwd; no residual, no e4m3 copy)."""
     K, M = g.K, g.M
+    if spd:
+        y = out if out is not None else new_act(g.N, 4 * K, g.OH // 2, g.OW // 2, z)
+        call('dmy_bn_act_s2d_fwd', dcode(z), ptr(z), K, ptr(scale), ptr(shift), spec.act, ptr(y), yps, g.N, g.OH, g.OW,
+             K, stream())
+        return y
     y = out if out is not None else new_act(g.N, K, g.OH, g.OW, z)
     emit = spec.f8_emit if (emit_ok and F8_DELAYED[0] and z.dtype == torch.bfloat16 and K % 8 == 0 and yps % 8 == 0 and
                             (res is None or rps % 8 == 0)) else None
@@ -768,10 +801,10 @@ def _act_pass(g, z, scale, shift, spec, res, rps, out, yps, emit_ok):
     return y
 
 
-def _save_ctx(ctx, saved, g, spec, train_bn, bnlink, weight, bias, gamma, beta, has_res, xsink, rsink):
+def _save_ctx(ctx, saved, g, spec, train_bn, bnlink, weight, bias, gamma, beta, has_res, xsink, rsink, spd=False):
     """everything ConvBNActFn.backward reads, set in this one place"""
     ctx.save_for_backward(*saved)
-    ctx.g, ctx.spec, ctx.train_bn, ctx.bnlink = g, spec, train_bn, bnlink
+    ctx.g, ctx.spec, ctx.train_bn, ctx.bnlink, ctx.spd = g, spec, train_bn, bnlink, spd
     ctx.has_bias, ctx.has_res, ctx.xsink, ctx.rsink = bias is not None, has_res, xsink, rsink
     ctx.arena, ctx.wkey = WgradArena.current, weight.data_ptr()
     ctx.pkeys = tuple(t.data_ptr() if t is not None else None for t in (bias, gamma, beta))
@@ -807,6 +840,11 @@ def _bn_bwd_coef(ctx, dt, dy, dps, z, stats, gamma):
         rd, link.ready = link.ready, None
     if rd is not None and rd[0].data_ptr() == dy.data_ptr() and rd[1] == dps and rd[0]._version == rd[5]:
         _, _, pdb, pdg, P, _ = rd  # written by the consumer (data-grad epilogue / SCConv gate)
+    elif ctx.spd:  # dy is in SM layout: the reduce reads it through the mapping, z in row order
+        P = call('dmy_bn_bwd_reduce_s2d_rows', dt, M, K)
+        pdb, pdg = f32(P * K, dev), f32(P * K, dev)
+        call('dmy_bn_bwd_reduce_s2d', dt, ptr(z), K, ptr(dy), dps, *map(ptr, stats), ctx.spec.act, ctx.g.N, ctx.g.OH,
+             ctx.g.OW, K, ptr(pdb), ptr(pdg), stream())
     else:
         P = call('dmy_bn_reduce_rows', dt, ptr(z), K, ptr(dy), dps, M, K)
         pdb, pdg = f32(P * K, dev), f32(P * K, dev)
@@ -852,7 +890,12 @@ def _act_bias_bwd(ctx, dt, dy, dps, z):
     affine map; dz is dy itself behind ACT_NONE) and the bias gradient, the column sums of dz"""
     K, M, dev = ctx.g.K, ctx.g.M, dy.device
     dz, dzps, dbias = dy, dps, None
-    if ctx.spec.act != ACT_NONE:
+    if ctx.spd:  # the same pass also undoes the SM fold, so it runs behind ACT_NONE too
+        dz, dzps = new_act(ctx.g.N, K, ctx.g.OH, ctx.g.OW, z), K
+        zero, one = const_vec(K, 0.0, dev), const_vec(K, 1.0, dev)
+        call('dmy_bn_bwd_apply_s2d', dt, ptr(z), K, ptr(dy), dps, ptr(one), ptr(zero), ptr(zero), ptr(one),
+             ctx.spec.act, ptr(one), ptr(zero), ptr(zero), ptr(dz), K, ctx.g.N, ctx.g.OH, ctx.g.OW, K, stream())
+    elif ctx.spec.act != ACT_NONE:
         dz, dzps = new_act(ctx.g.N, K, ctx.g.OH, ctx.g.OW, z), K
         zero, one = const_vec(K, 0.0, dev), const_vec(K, 1.0, dev)
         call('dmy_bn_bwd_apply', dt, ptr(z), K, ptr(dy), dps, ptr(one), ptr(zero), ptr(zero), ptr(one),
@@ -920,8 +963,9 @@ def _conv_wgrad(ctx, dt, x, dz, dzps):
 
 class ConvBNActFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, x, weight, bias, gamma, beta, res, spec, xsink=None, rsink=None, grad_on=True, out=None):
-        """out: None or [view] -- see out_view; ignored by a layer with no separate activation pass"""
+    def forward(ctx, x, weight, bias, gamma, beta, res, spec, xsink=None, rsink=None, grad_on=True, out=None, spd=False):
+        """out: None or [view] -- see out_view; ignored by a layer with no separate activation pass.  spd: the layer's
+        output is SM(act(bn(conv(x)))), (N, 4K, OH / 2, OW / 2) -- see conv_bn_act"""
         f8in, prod = getattr(x, '_dmy_f8', None), getattr(x, '_dmy_prod', None)
         # ctx.needs_input_grad mirrors requires_grad even when the CALLER runs under torch.no_grad() (forward itself
         # always runs with grad disabled): `grad_on` is the caller's grad mode, so a no-grad call (detect / val with
@@ -933,29 +977,32 @@ class ConvBNActFn(torch.autograd.Function):
         x, g, wf, wt, wkey = _conv_operands(x, weight, spec, need_grad, infer)
         f8 = _conv_fp8(x, g, weight, spec, wkey, f8in, prod, infer)
         res, rps = pixel_stride(res) if res is not None else (None, 0)
-        act_pass = bn is not None or spec.act != ACT_NONE or res is not None
-        out, yps = out_view(out and out[0], (g.N, g.K, g.OH, g.OW), x) if act_pass else (None, None)
-        yps = g.K if out is None else yps
+        oshape = _spd_shape(g, x, res) if spd else (g.N, g.K, g.OH, g.OW)
+        act_pass = spd or bn is not None or spec.act != ACT_NONE or res is not None
+        out, yps = out_view(out and out[0], oshape, x) if act_pass else (None, None)
+        yps = oshape[1] if out is None else yps
+        if infer and spd:
+            return _conv_infer_spd(x, g, wf, bias, spec, out, yps, f8)
         if infer:
             return _conv_infer(x, g, wf, bias, spec, res, rps, out, yps, f8)
         z, link = new_act(g.N, g.K, g.OH, g.OW, x), None
         if bn is None:
             _launch_conv_fwd(x, g, wf, bias, z, g.K, None, None, f8=f8)
             y = _act_pass(g, z, const_vec(g.K, 1.0, x.device), const_vec(g.K, 0.0, x.device), spec, res, rps, out, yps,
-                          False) if act_pass else z
+                          False, spd) if act_pass else z
             saved = (x, wt, z)
         else:
             stats = _conv_bn_stats(x, g, wf, bias, z, bn, train_bn, f8)
             saved = (x, wt, z, *stats, bn.weight)
             if (spec.defer and DEFER_AFFINE[0] and train_bn and need_grad and x.dtype == torch.bfloat16 and
                     spec.act == ACT_NONE and res is None and out is None and g.K % 8 == 0 and f8 is None and
-                    g.groups == 1):
+                    g.groups == 1 and not spd):
                 y, link = z, _defer_affine(z, stats, spec.act, g.K)
             else:
-                y = _act_pass(g, z, stats[0], stats[1], spec, res, rps, out, yps, True)
-                if x.dtype == torch.bfloat16 and g.K % 128 == 0 and train_bn:
+                y = _act_pass(g, z, stats[0], stats[1], spec, res, rps, out, yps, True, spd)
+                if x.dtype == torch.bfloat16 and g.K % 128 == 0 and train_bn and not spd:
                     y._dmy_prod = spec  # an fp8 consumer may ask this layer to emit its e4m3 copy (F8Emit)
-        _save_ctx(ctx, saved, g, spec, train_bn, link, weight, bias, gamma, beta, res is not None, xsink, rsink)
+        _save_ctx(ctx, saved, g, spec, train_bn, link, weight, bias, gamma, beta, res is not None, xsink, rsink, spd)
         return y
 
     @staticmethod
@@ -964,12 +1011,18 @@ class ConvBNActFn(torch.autograd.Function):
         x, wt, z, *bnt = ctx.saved_tensors
         dy, dps = pixel_stride(dy.to(z.dtype))
         K, dev, dt = g.K, dy.device, dcode(dy)
+        if ctx.spd and (dps % VW[dy.dtype] or dy.data_ptr() % 16):  # the SM passes read dy as 16-byte vectors
+            dy, dps = pixel_stride(dy.contiguous(memory_format=CL))
         dbias = dgamma = dbeta = fused = None
         if spec.bn is not None:
             *stats, gamma = bnt
             *coef, dgamma, dbeta = _bn_bwd_coef(ctx, dt, dy, dps, z, stats, gamma)
-            fused = _bwd1x1(ctx, dy, dps, x, wt, z, stats, coef)
-            if fused is None:
+            fused = None if ctx.spd else _bwd1x1(ctx, dy, dps, x, wt, z, stats, coef)
+            if ctx.spd:
+                dz, dzps = new_act(g.N, K, g.OH, g.OW, z), K
+                call('dmy_bn_bwd_apply_s2d', dt, ptr(z), K, ptr(dy), dps, *map(ptr, stats), spec.act, *map(ptr, coef),
+                     ptr(dz), K, g.N, g.OH, g.OW, K, stream())
+            elif fused is None:
                 dz, dzps = new_act(g.N, K, g.OH, g.OW, z), K
                 call('dmy_bn_bwd_apply', dt, ptr(z), K, ptr(dy), dps, *map(ptr, stats), spec.act, *map(ptr, coef),
                      ptr(dz), K, g.M, K, stream())
@@ -983,14 +1036,18 @@ class ConvBNActFn(torch.autograd.Function):
             dx = _dgrad(ctx, dt, dz, dzps, wt, z) if ctx.needs_input_grad[0] else None
             dw = _conv_wgrad(ctx, dt, x, dz, dzps) if ctx.needs_input_grad[1] else None
         dres = (dy if ctx.rsink is None else ctx.rsink.passthrough(dy)) if ctx.has_res else None
-        return dx, dw, dbias, dgamma, dbeta, dres, None, None, None, None, None
+        return dx, dw, dbias, dgamma, dbeta, dres, None, None, None, None, None, None
 
 
 def conv_bn_act(x, weight, bias, bn, stride, pad, act, res=None, spec=None, xsink=None, rsink=None, out=None,
-                defer=False):
+                defer=False, spd=False):
     """xsink / rsink: GradSinks collecting the gradient of x / of the residual (see GradSink).  out: an NHWC view
     (a concat_buffer channel slice) the activation is written into instead of a fresh tensor, when the layer has a
-    separate activation pass (BN and / or act / residual); the returned tensor is then that view."""
+    separate activation pass (BN and / or act / residual); the returned tensor is then that view.
+    spd: the layer is followed by SM (models/common.py:1460-1467) and returns (N, 4K, OH / 2, OW / 2), `out` being a
+    view of that shape.  Train mode folds SM into the activation pass and into the backward's reduce / apply passes
+    (csrc/spd.hip); inference runs the one-launch conv into a temporary and dmy_space_to_depth into the destination.
+    Such a layer takes no residual and never the deferred-affine exit, the fused 1x1 backward or the fp8 emit."""
     if spec is None:  # a persistent spec per weight PARAMETER (views made per call share their base), so the
         # inference caches (prepped weight, eval BN coefficients) hold across calls for the Detect / Swin / CBAM convs
         spec = _param_spec(weight._base if weight._base is not None else weight, stride, pad, act, bn)
@@ -998,7 +1055,7 @@ def conv_bn_act(x, weight, bias, bn, stride, pad, act, res=None, spec=None, xsin
     gamma = bn.weight if bn is not None else None
     beta = bn.bias if bn is not None else None
     return ConvBNActFn.apply(x, weight, bias, gamma, beta, res, spec, xsink, rsink, torch.is_grad_enabled(),
-                             [out] if out is not None else None)
+                             [out] if out is not None else None, bool(spd))
 
 
 # ------------------------------------------------------------------ pooling / resize / concat
@@ -1050,6 +1107,83 @@ def maxpool_chain3(x, k, outs=(None, None, None)):
     call('dmy_maxpool_chain3_fwd', dcode(x), ptr(x), xps, ptr(ys[0]), ptr(ys[1]), ptr(ys[2]), yps, N, H, W, C, k,
          stream())
     return tuple(ys)
+
+
+def _spd_vec(what, C, dtype):
+    if C % VW[dtype] or C // VW[dtype] > 256:
+        raise NotImplementedError(f'{what} (csrc/spd.hip) takes whole 16-byte vectors, at most 256 per pixel: channels '
+                                  f'multiples of {VW[dtype]} for {dtype}, got {C}')
+
+
+def _vec_addressable(t):
+    """(t', ps) as pixel_stride, copied dense when the view is not 16-byte-vector addressable (an odd slice offset)"""
+    t, ps = pixel_stride(t)
+    if ps % VW[t.dtype] or t.data_ptr() % 16:
+        t = t.contiguous(memory_format=CL)
+        ps = t.shape[1]
+    return t, ps
+
+
+class MaxPool2Fn(torch.autograd.Function):
+    """nn.MaxPool2d(2, 2) (MP, models/common.py:1469-1475): dmy_maxpool2_fwd keeps the window offset of each maximum,
+    the backward gathers through it.  sink: the GradSink of x when x has other consumers (DMMConv)."""
+
+    @staticmethod
+    def forward(ctx, x, sink=None):
+        dcode(x)
+        x, xps = _vec_addressable(x)
+        N, C, H, W = x.shape
+        _spd_vec('the 2 x 2 max pool', C, x.dtype)
+        if H < 2 or W < 2:
+            raise ValueError(f'MaxPool2d(2, 2) needs a map of at least 2 x 2, got {H}x{W}')
+        y = new_act(N, C, H // 2, W // 2, x)
+        arg = torch.empty((N, H // 2, W // 2, C), dtype=torch.uint8, device=x.device)
+        call('dmy_maxpool2_fwd', dcode(x), ptr(x), xps, ptr(y), C, ptr(arg), N, H, W, C, stream())
+        ctx.save_for_backward(arg)
+        ctx.shape, ctx.sink = (N, C, H, W), sink
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        (arg,) = ctx.saved_tensors
+        N, C, H, W = ctx.shape
+        dy, dps = _vec_addressable(dy)
+        buf, bps, acc = sink_target(ctx.sink, N, C, H, W, dy)
+        call('dmy_maxpool2_bwd', dcode(dy), ptr(dy), dps, ptr(arg), ptr(buf), bps, acc, N, H, W, C, stream())
+        return sink_result(ctx.sink, buf), None
+
+
+class SpdSplitFn(torch.autograd.Function):
+    """DMMConv2's front end (models/common.py:1516, 1519): one pass over x writes SM(x) into `out` (the first 4C
+    channels of the module's concat buffer, or a fresh tensor) and MP(x) with its argmax; the backward is one launch,
+    dx = SM^-1(d_sm) + the pool's gather of d_mp.  -> (sm, mp)"""
+
+    @staticmethod
+    def forward(ctx, x, out=None):
+        dcode(x)
+        x, xps = _vec_addressable(x)
+        N, C, H, W = x.shape
+        even_hw(H, W, 'SM / DMMConv2')
+        _spd_vec('the SM / MP split', C, x.dtype)
+        sm, smps = out_view(out and out[0], (N, 4 * C, H // 2, W // 2), x)
+        if sm is None:
+            sm, smps = new_act(N, 4 * C, H // 2, W // 2, x), 4 * C
+        mp = new_act(N, C, H // 2, W // 2, x)
+        arg = torch.empty((N, H // 2, W // 2, C), dtype=torch.uint8, device=x.device)
+        call('dmy_spd_split_fwd', dcode(x), ptr(x), xps, ptr(sm), smps, ptr(mp), C, ptr(arg), N, H, W, C, stream())
+        ctx.save_for_backward(arg)
+        ctx.shape = (N, C, H, W)
+        return sm, mp
+
+    @staticmethod
+    def backward(ctx, dsm, dmp):
+        (arg,) = ctx.saved_tensors
+        N, C, H, W = ctx.shape
+        dsm, dsps = _vec_addressable(dsm)
+        dmp, dmps = _vec_addressable(dmp)
+        dx = new_act(N, C, H, W, dsm)
+        call('dmy_spd_split_bwd', dcode(dsm), ptr(dsm), dsps, ptr(dmp), dmps, ptr(arg), ptr(dx), C, N, H, W, C, stream())
+        return dx, None
 
 
 class AvgPoolFn(torch.autograd.Function):

@@ -20,7 +20,8 @@ from ..functional import ACT_NONE, ACT_SILU, ACT_HARDSWISH, ACT_SIGMOID, ACT_GEL
 __all__ = ['autopad', 'Conv', 'DWConv', 'GhostConv', 'GhostBottleneck', 'C3Ghost', 'Bottleneck', 'C3', 'SPPF', 'SPPFCSPC', 'SCConv', 'CoorAttention', 'CA',
            'CABottleneck', 'C3CA', 'Concat', 'AdConcat2', 'AdConcat3', 'AdaptConcat', 'Adapt_Add2', 'Adapt_Add3', 'AdaptADD',
            'Upsample', 'C3STR', 'SwinTransformerBlock',
-           'SwinTransformerLayer', 'WindowAttention', 'Mlp', 'DropPath', 'space_to_depth', 'SPP', 'CBAM',
+           'SwinTransformerLayer', 'WindowAttention', 'Mlp', 'DropPath', 'space_to_depth', 'SM', 'MP', 'DMConv', 'DMMConv',
+           'DMMConv2', 'SPP', 'CBAM',
            'ChannelAttentionModule', 'SpatialAttentionModule', 'C3TR', 'TransformerBlock', 'TransformerLayer']
 
 
@@ -528,6 +529,94 @@ class space_to_depth(nn.Module):
 
     def forward(self, x):
         return Fn.SpaceToDepthFn.apply(x)
+
+
+class SM(space_to_depth):
+    """models/common.py:1460-1467: the same cat as space_to_depth under the name the DM YAMLs use."""
+
+    def forward(self, x):
+        Fn.even_hw(x.shape[2], x.shape[3], 'SM')
+        return Fn.SpaceToDepthFn.apply(x)
+
+
+class MP(nn.Module):
+    """models/common.py:1469-1475: nn.MaxPool2d(k, k).  Only k = 2 has a kernel (dmy_maxpool2_*); `m` is kept for the
+    reference's attribute (it has no parameters)."""
+
+    def __init__(self, k=2):
+        super().__init__()
+        if k != 2:
+            raise NotImplementedError(f'MP(k={k}): only the 2 x 2 stride-2 max pool has a gfx950 kernel')
+        self.m = nn.MaxPool2d(kernel_size=k, stride=k)
+
+    def forward(self, x, sink=None):
+        return Fn.MaxPool2Fn.apply(x, sink)
+
+
+def _spd_conv(m, x, xsink=None, out=None):
+    """a Conv followed by SM, as one spd layer (Fn.conv_bn_act(spd=True))"""
+    c, bn = m.conv, getattr(m, 'bn', None)
+    assert c.dilation in (1, (1, 1)), 'dilated conv not on the DMA-YOLO path'
+    s, pad, a = c.stride[0], _pad_int(c.padding), act_code(m.act)
+    return Fn.conv_bn_act(x, c.weight, c.bias, bn, s, pad, a, spec=Fn.spec_for(c, s, pad, a, bn), xsink=xsink, out=out,
+                          spd=True)
+
+
+class DMConv(nn.Module):
+    """models/common.py:1538-1547: SM(cv1(x)), cv1 a 3x3 stride-1 Conv -> (N, 4 c2, H / 2, W / 2).  One spd layer: SM
+    is folded into cv1's activation pass and into its backward's BN passes."""
+
+    def __init__(self, c1, c2):
+        super().__init__()
+        self.cv1 = Conv(c1, c2, 3, 1)
+        self.sm = SM()
+
+    def forward(self, x, out=None):
+        Fn.even_hw(x.shape[2], x.shape[3], 'DMConv')
+        return _spd_conv(self.cv1, x, out=out)
+
+
+class DMMConv(nn.Module):
+    """models/common.py:1523-1536: cat(SM(cv2(x)), cv1(MP(x))) -> (N, 5 c2, H / 2, W / 2).  One concat buffer: cv2 (3x3,
+    spd) writes the first 4 c2 channels, cv1 over the pooled map the last c2, so the concat copies nothing.  x feeds
+    the pool and cv2: their input gradients meet in one GradSink."""
+
+    def __init__(self, c1, c2):
+        super().__init__()
+        self.cv1 = Conv(c1, c2, 1, 1)
+        self.cv2 = Conv(c1, c2, 3, 1)
+        self.sm = SM()
+        self.mp = MP()
+
+    def forward(self, x):
+        N, _, H, W = x.shape
+        Fn.even_hw(H, W, 'DMMConv')
+        c2 = self.cv2.conv.out_channels
+        cat = Fn.concat_buffer(N, 5 * c2, H // 2, W // 2, x)
+        sk = Fn.GradSink(2)
+        a = _spd_conv(self.cv2, x, xsink=sk, out=cat[:, :4 * c2])
+        b = self.cv1(self.mp(x, sk), out=cat[:, 4 * c2:])
+        return Fn.ConcatFn.apply(None, 0.0, None, a, b)
+
+
+class DMMConv2(nn.Module):
+    """models/common.py:1508-1521: cat(SM(x), cv1(MP(x))) -> (N, 4 c1 + c2, H / 2, W / 2).  Fn.SpdSplitFn reads x once
+    and writes SM(x) into the first 4 c1 channels of the concat buffer and the pooled map; cv1 writes the last c2."""
+
+    def __init__(self, c1, c2):
+        super().__init__()
+        self.cv1 = Conv(c1, c2, 1, 1)
+        self.sm = SM()
+        self.mp = MP()
+
+    def forward(self, x):
+        N, c1, H, W = x.shape
+        Fn.even_hw(H, W, 'DMMConv2')
+        c2 = self.cv1.conv.out_channels
+        cat = Fn.concat_buffer(N, 4 * c1 + c2, H // 2, W // 2, x)
+        a, p = Fn.SpdSplitFn.apply(x, [cat[:, :4 * c1]])
+        b = self.cv1(p, out=cat[:, 4 * c1:])
+        return Fn.ConcatFn.apply(None, 0.0, None, a, b)
 
 
 class _AddConv(nn.Sequential):

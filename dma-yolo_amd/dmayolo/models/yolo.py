@@ -20,7 +20,7 @@ import torch.nn as nn
 from .. import functional as Fn
 from ..functional import call, ptr, stream, dcode
 from .common import *  # noqa: F401,F403  (the YAML namespace)
-from .common import Conv, Upsample, SCConv, GhostConv, GhostBottleneck, autopad, space_to_depth
+from .common import Conv, Upsample, SCConv, GhostConv, GhostBottleneck, autopad, space_to_depth, MP, DMConv, DMMConv, DMMConv2
 from .tdetect import TDetect
 from ..utils.general import make_divisible
 from ..utils.torch_utils import initialize_weights, fuse_conv_and_bn
@@ -127,7 +127,7 @@ def _out_hw(m, hw):
     if isinstance(m, nn.Upsample):
         sf = m.scale_factor if isinstance(m.scale_factor, (int, float)) else m.scale_factor[0]
         return (int(hw[0] * sf), int(hw[1] * sf))
-    if isinstance(m, space_to_depth):
+    if isinstance(m, (space_to_depth, MP, DMConv, DMMConv, DMMConv2)):  # SM is a space_to_depth
         return (hw[0] // 2, hw[1] // 2)
     return hw
 
@@ -548,9 +548,15 @@ def parse_model(d, ch):
                 args[1] = [list(range(args[1] * 2))] * len(f)
         elif m is TDetect:
             args.append([ch[x] for x in f])
-        elif m is space_to_depth:
+        elif m in (space_to_depth, C.SM):
             c2 = 4 * ch[f]
-        elif m is Upsample:
+        elif m is DMMConv:  # models/yolo.py:451-462: no width multiple, no make_divisible
+            c1, c2, args = ch[f], 5 * args[0], [ch[f], args[0]]
+        elif m is DMMConv2:
+            c1, c2, args = ch[f], args[0] + 4 * ch[f], [ch[f], args[0]]
+        elif m is DMConv:
+            c1, c2, args = ch[f], 4 * args[0], [ch[f], args[0]]
+        elif m in (Upsample, MP):
             c2 = ch[f]
         else:
             raise NotImplementedError(f'YAML module {m} is outside the DMA-YOLO hot path')

@@ -252,6 +252,45 @@ int dmy_bn_reduce_rows(int dtype, const void* z, long zps, const void* dy, long 
 int dmy_colsum2_rows(long P);
 int dmy_colsum2(const float* a, const float* b, long P, int C, float* oa, float* ob, void* stream);
 
+/* ---- SPD-mix downsamplers (csrc/spd.hip): DMConv / DMMConv / DMMConv2 with SM and MP (models/common.py:1460-1475,
+ *      1508-1547).  Streaming NHWC kernels, fp32 arithmetic, no atomics.  Supported: bf16 with every channel count and
+ *      pixel stride a multiple of 8, fp32 a multiple of 4, at most 256 vectors per row, 16-byte aligned bases; anything
+ *      else returns hipErrorInvalidValue and launches nothing.
+ *      SM layout (models/common.py:1467): the full-resolution pixel (n, h, w) with K channels is the K-channel block
+ *      q = (h & 1) + 2 * (w & 1) of the half-resolution pixel (n, h / 2, w / 2); H and W even. */
+/* Conv.bn + Conv.act + SM of DMConv / DMMConv.cv2 (models/common.py:1533-1534, 1544-1545): y_sm = act(z * scale +
+ * shift), z [N][H][W][K] with pixel stride zps, y_sm [N][H/2][W/2][4K] with pixel stride yps >= 4K.  dmy_bn_act_fwd's
+ * per-element math (no residual, no fp8 emit) stored through the SM mapping. */
+int dmy_bn_act_s2d_fwd(int dtype, const void* z, long zps, const float* scale, const float* shift, int act, void* y,
+                       long yps, int N, int H, int W, int K, void* stream);
+/* the backward of the same lines: dmy_bn_bwd_reduce / dmy_bn_bwd_apply with dy [N][H/2][W/2][4K] (pixel stride dps)
+ * read through the SM mapping and z / dz in plain row order.  The reduce writes dmy_bn_bwd_reduce_s2d_rows(dtype, M =
+ * N * H * W, K) partial rows of K floats to pdb and pdg, every row written, rows visited in a fixed order; they feed
+ * dmy_colsum2 / dmy_bn_bwd_finalize like dmy_bn_bwd_reduce's. */
+int dmy_bn_bwd_reduce_s2d_rows(int dtype, long M, int K);
+int dmy_bn_bwd_reduce_s2d(int dtype, const void* z, long zps, const void* dy, long dps, const float* scale,
+                          const float* shift, const float* mean, const float* invstd, int act, int N, int H, int W,
+                          int K, float* pdb, float* pdg, void* stream);
+int dmy_bn_bwd_apply_s2d(int dtype, const void* z, long zps, const void* dy, long dps, const float* scale,
+                         const float* shift, const float* mean, const float* invstd, int act, const float* ca,
+                         const float* cb, const float* cc, void* dz, long dzps, int N, int H, int W, int K,
+                         void* stream);
+/* nn.MaxPool2d(2, 2) of MP (models/common.py:1469-1475): y [N][H/2][W/2][C] (floor), argmax [N * (H/2) * (W/2)][C]
+ * the window offset dh * 2 + dw of the maximum under ATen's rule (first maximum in (row, column) scan order, a NaN
+ * wins).  The backward is a gather over dx [N][H][W][C]: every input pixel belongs to at most one window; accumulate
+ * as in dmy_maxpool_bwd (dx += for GradSink targets). */
+int dmy_maxpool2_fwd(int dtype, const void* x, long xps, void* y, long yps, unsigned char* argmax, int N, int H, int W,
+                     int C, void* stream);
+int dmy_maxpool2_bwd(int dtype, const void* dy, long dps, const unsigned char* argmax, void* dx, long dxps,
+                     int accumulate, int N, int H, int W, int C, void* stream);
+/* DMMConv2's front end (models/common.py:1516, 1519): x is read once; sm [N][H/2][W/2][4C] (pixel stride smps) takes
+ * SM(x), mp [N][H/2][W/2][C] and argmax take MP(x) as dmy_maxpool2_fwd writes them.  The backward writes dx =
+ * SM^-1(dsm) + the pool's gather of dmp, summed in fp32 and rounded once, one write per element.  H and W even. */
+int dmy_spd_split_fwd(int dtype, const void* x, long xps, void* sm, long smps, void* mp, long mpps,
+                      unsigned char* argmax, int N, int H, int W, int C, void* stream);
+int dmy_spd_split_bwd(int dtype, const void* dsm, long dsmps, const void* dmp, long dmpps, const unsigned char* argmax,
+                      void* dx, long dxps, int N, int H, int W, int C, void* stream);
+
 /* ---- memory-bound NHWC ops */
 /* nn.MaxPool2d(k, 1, k//2): SPPF common.py:250-258, SPPFCSPC :1266-1274 */
 int dmy_maxpool_fwd(int dtype, const void* x, long xps, void* y, long yps, unsigned char* argmax, int N, int H, int W,
