@@ -1,6 +1,7 @@
 // Depthwise convolution (groups == C_in == C_out, one k x k filter per channel) for gfx950: forward with the BN
 // partial sums or the one-launch inference epilogue, data-grad as a gather, weight-grad through per-block partial
-// rows summed in row order.  Replaces nn.Conv2d(groups=c) in DWConv / GhostConv.cv2 (models/common.py:79-82, 666-699).
+// rows summed in row order.  Replaces nn.Conv2d(groups=c) in DWConv / GhostConv.cv2 (models/common.py:79-82, 666-699)
+// and the biased 7 x 7 of get_dwconv in GnConv (:1329, 1361-1362), whose bias gradient rides on the weight-grad launch.
 //
 // There is no reduction over channels, so no MFMA: these are streaming kernels over NHWC.  A thread owns one 16-byte
 // channel vector (weight-grad: 4 channels) of a strip of kTW consecutive output pixels along W, so the (kTW - 1) * S + K
@@ -22,7 +23,7 @@ namespace {
 constexpr int kTW = 4;            // output pixels per thread along W
 constexpr int kFwdRowCap = 1024;  // BN partial rows (== gridDim.x of the forward)
 constexpr int kWgRowCap = 512;    // weight-grad partial rows (== gridDim.x of the weight-grad)
-constexpr int kWgC = 4;           // channels per thread in the weight-grad (K * K * 4 accumulators)
+constexpr int kWgC = 4;           // channels per thread in the weight-grad (K * K * 4 accumulators; K = 7: K * 4)
 
 // channel units per block tile: the next power of two for <= 32 units, else the one of 32 / 16 / 8 that pads least
 int tile_log2(int units) {
@@ -340,14 +341,100 @@ dw_wgrad_kernel(const T* __restrict__ x, const T* __restrict__ dz, float* __rest
   }
 }
 
-// dw[c][tap] (torch OIHW of a (C, 1, K, K) weight) = (accumulate ? dw : 0) + the partial rows summed in row order
+// The weight-grad of a wide filter (K = 7), one filter row per blockIdx.z: K * kWgC accumulators per thread instead of
+// K * K * kWgC (196 at K = 7, which would not stay in registers).  Same partial rows as dw_wgrad_kernel, RL floats apart:
+// part[blockIdx.x][(i * K + j) * C + c] for i = blockIdx.z.  bias != 0: the blocks of filter row 0 also write the bias
+// gradient's share part[blockIdx.x][K * K * C + c] = sum over this block's dz pixels of dz[n, oh, ow, c] (RL >= (K * K + 1) * C).
+template <typename T, int K, int S>
 __global__ void __launch_bounds__(256)
-dw_wgrad_finalize_kernel(const float* __restrict__ part, int rows, int C, int KK, float* __restrict__ dw, int accumulate) {
+dw_wgrad_row_kernel(const T* __restrict__ x, const T* __restrict__ dz, float* __restrict__ part, long RL, int bias, int N,
+                    int H, int W, int C, long xps, int OH, int OW, long zps, int tcl) {
+  constexpr int P = K / 2, NC = (kTW - 1) * S + K;
+  const int TC = 1 << tcl, cu = threadIdx.x & (TC - 1), slot = threadIdx.x >> tcl, PIX = 256 >> tcl;
+  const int c4 = blockIdx.y * TC + cu, i = blockIdx.z;
+  const bool cok = c4 < C / kWgC, bsum = bias && i == 0;  // bsum is block-uniform
+  const int c0 = cok ? c4 * kWgC : 0;
+  const int SW = (OW + kTW - 1) / kTW;
+  const long nstrips = (long)N * OH * SW, ngroups = (nstrips + PIX - 1) / PIX;
+  float acc[K][kWgC], bacc[kWgC];
+#pragma unroll
+  for (int e = 0; e < kWgC; ++e) {
+    bacc[e] = 0.f;
+#pragma unroll
+    for (int j = 0; j < K; ++j) acc[j][e] = 0.f;
+  }
+  for (long g = blockIdx.x; g < ngroups; g += gridDim.x) {
+    const long st = g * PIX + slot;
+    if (!cok || st >= nstrips) continue;
+    const Strip sp = strip_of(st, OH, SW);
+    float zv[kTW][kWgC];
+    const T* zr = dz + ((long)sp.n * OH + sp.oh) * OW * zps + c0;
+#pragma unroll
+    for (int b = 0; b < kTW; ++b) {
+      const bool ok = sp.ow0 + b < OW;
+      load4(zr + (long)(ok ? sp.ow0 + b : sp.ow0) * zps, zv[b]);
+#pragma unroll
+      for (int e = 0; e < kWgC; ++e) zv[b][e] = ok ? zv[b][e] : 0.f;
+    }
+    if (bsum) {
+#pragma unroll
+      for (int b = 0; b < kTW; ++b)
+#pragma unroll
+        for (int e = 0; e < kWgC; ++e) bacc[e] += zv[b][e];
+    }
+    const int ih = sp.oh * S - P + i;
+    if (ih < 0 || ih >= H) continue;
+    const T* xr = x + ((long)sp.n * H + ih) * W * xps + c0;
+#pragma unroll
+    for (int jj = 0; jj < NC; ++jj) {
+      const int iw = sp.ow0 * S - P + jj;
+      const bool ok = iw >= 0 && iw < W;
+      float xv[kWgC];
+      load4(xr + (long)(ok ? iw : 0) * xps, xv);
+#pragma unroll
+      for (int b = 0; b < kTW; ++b) {
+        const int j = jj - b * S;
+        if (j >= 0 && j < K) {
+#pragma unroll
+          for (int e = 0; e < kWgC; ++e) acc[j][e] += (ok ? xv[e] : 0.f) * zv[b][e];
+        }
+      }
+    }
+  }
+  __shared__ float red[4][32 * kWgC];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nch = TC * kWgC;
+  float* row = part + (long)blockIdx.x * RL;
+#pragma unroll
+  for (int j = 0; j <= K; ++j) {
+    if (j == K && !bsum) break;
+#pragma unroll
+    for (int e = 0; e < kWgC; ++e) {
+      const float a = unit_sum(j < K ? acc[j % K][e] : bacc[e], tcl);  // j == K: the bias share
+      if (lane < TC) red[wave][lane * kWgC + e] = a;
+    }
+    __syncthreads();
+    if ((int)threadIdx.x < nch) {
+      const int ch = blockIdx.y * nch + threadIdx.x;
+      if (ch < C) row[(long)(j < K ? i * K + j : K * K) * C + ch] = ((red[0][threadIdx.x] + red[1][threadIdx.x]) + red[2][threadIdx.x]) + red[3][threadIdx.x];
+    }
+    __syncthreads();
+  }
+}
+
+// dw[c][tap] (torch OIHW of a (C, 1, K, K) weight) = (accumulate ? dw : 0) + the partial rows (RL floats apart) summed
+// in row order; db (nullable): the same for the bias gradient, whose share of a row follows its KK * C filter taps
+__global__ void __launch_bounds__(256)
+dw_wgrad_finalize_kernel(const float* __restrict__ part, int rows, int C, int KK, long RL, float* __restrict__ dw,
+                         int accumulate, float* __restrict__ db, int db_accumulate) {
   const int e = blockIdx.x * 256 + threadIdx.x;
-  if (e >= KK * C) return;
+  if (e >= (KK + (db ? 1 : 0)) * C) return;
   const int tap = e / C, c = e - tap * C;
   float s = 0.f;
-  for (int p = 0; p < rows; ++p) s += part[(long)p * KK * C + e];
+  for (int p = 0; p < rows; ++p) s += part[(long)p * RL + e];
+  if (tap == KK) {
+    db[c] = db_accumulate ? db[c] + s : s;
+    return;
+  }
   const long o = (long)c * KK + tap;
   dw[o] = accumulate ? dw[o] + s : s;
 }
@@ -358,7 +445,7 @@ bool geom_ok(int dtype, int N, int H, int W, int C, long xps, int KH, int KW, in
   const int VW = dtype ? 8 : 4;
   if (dtype != 0 && dtype != 1) return false;
   if (N < 1 || H < 1 || W < 1 || C < VW || C % VW) return false;
-  if (KH != KW || (KH != 3 && KH != 5) || (S != 1 && S != 2) || P != KH / 2) return false;
+  if (KH != KW || (KH != 3 && KH != 5 && KH != 7) || (S != 1 && S != 2) || (KH == 7 && S != 1) || P != KH / 2) return false;
   if (OH != (H + 2 * P - KH) / S + 1 || OW != (W + 2 * P - KW) / S + 1 || OH < 1 || OW < 1) return false;
   if (xps < C || zps < C || xps % VW || zps % VW) return false;
   if ((long)N * H * W >= (1L << 31) || (long)N * OH * OW >= (1L << 31)) return false;
@@ -375,8 +462,9 @@ int rows_for(long M, int cap) {
     constexpr int K_ = KK, S_ = SS;              \
     __VA_ARGS__;                                 \
   }
-#define DW_DISPATCH(...)                                                                              \
+#define DW_DISPATCH35(...)                                                                            \
   DW_K_S(3, 1, __VA_ARGS__) DW_K_S(3, 2, __VA_ARGS__) DW_K_S(5, 1, __VA_ARGS__) DW_K_S(5, 2, __VA_ARGS__)
+#define DW_DISPATCH(...) DW_DISPATCH35(__VA_ARGS__) DW_K_S(7, 1, __VA_ARGS__)  // k7 is stride 1 only (geom_ok)
 
 template <typename T, int EPI>
 int launch_fwd(const void* x, const void* w, const float* bias, void* y, float* psum, float* psq, int N, int H, int W,
@@ -402,19 +490,26 @@ int launch_dgrad(const void* dz, const void* w, void* dx, int accumulate, int N,
         (const T*)dz, (const T*)w, nullptr, (T*)dx, nullptr, nullptr, N, OH, OW, C, zps, H, W, xps, tcl, nullptr, nullptr,
         0, nullptr, 0, accumulate)))
   } else {
-    DW_DISPATCH(if (S_ == 2) (dw_dgrad_s2_kernel<T, K_><<<grid, 256, 0, st>>>(
+    DW_DISPATCH35(if (S_ == 2) (dw_dgrad_s2_kernel<T, K_><<<grid, 256, 0, st>>>(
         (const T*)dz, (const T*)w, (T*)dx, accumulate, N, H, W, C, xps, OH, OW, zps, tcl)))
   }
   return (int)hipGetLastError();
 }
 
+// RL: floats between partial rows; bias: the rows also carry the bias gradient's share (the row-per-z kernel only)
 template <typename T>
-int launch_wgrad(const void* x, const void* dz, float* part, int N, int H, int W, int C, long xps, int KH, int S, int OH,
-                 int OW, long zps, hipStream_t st) {
+int launch_wgrad(const void* x, const void* dz, float* part, long RL, int bias, int N, int H, int W, int C, long xps,
+                 int KH, int S, int OH, int OW, long zps, hipStream_t st) {
   const int tcl = tile_log2(C / kWgC);
-  dim3 grid(rows_for((long)N * OH * OW, kWgRowCap), ceil_div(C / kWgC, 1 << tcl));
-  DW_DISPATCH((dw_wgrad_kernel<T, K_, S_><<<grid, 256, 0, st>>>((const T*)x, (const T*)dz, part, N, H, W, C, xps, OH,
-                                                                   OW, zps, tcl)))
+  dim3 grid(rows_for((long)N * OH * OW, kWgRowCap), ceil_div(C / kWgC, 1 << tcl), KH == 7 ? 7 : 1);
+  if (KH == 7) {
+    dw_wgrad_row_kernel<T, 7, 1><<<grid, 256, 0, st>>>((const T*)x, (const T*)dz, part, RL, bias, N, H, W, C, xps, OH, OW,
+                                                       zps, tcl);
+    return (int)hipGetLastError();
+  }
+  if (bias) return -1;
+  DW_DISPATCH35((dw_wgrad_kernel<T, K_, S_><<<grid, 256, 0, st>>>((const T*)x, (const T*)dz, part, N, H, W, C, xps, OH,
+                                                                     OW, zps, tcl)))
   return (int)hipGetLastError();
 }
 
@@ -475,15 +570,34 @@ DMY_API int dmy_dwconv_wgrad(int dtype, const void* x, const void* dz, float* pa
                              int KH, int KW, int S, int P, int OH, int OW, long zps, void* stream) {
   if (!dmy_dwconv_ok(dtype, x, part, dz, N, H, W, C, C, C, xps, KH, KW, S, P, OH, OW, zps)) return -1;
   hipStream_t st = (hipStream_t)stream;
-  return dtype ? launch_wgrad<bf16>(x, dz, part, N, H, W, C, xps, KH, S, OH, OW, zps, st)
-               : launch_wgrad<float>(x, dz, part, N, H, W, C, xps, KH, S, OH, OW, zps, st);
+  const long RL = (long)KH * KW * C;
+  return dtype ? launch_wgrad<bf16>(x, dz, part, RL, 0, N, H, W, C, xps, KH, S, OH, OW, zps, st)
+               : launch_wgrad<float>(x, dz, part, RL, 0, N, H, W, C, xps, KH, S, OH, OW, zps, st);
+}
+
+DMY_API int dmy_dwconv_wgrad_bias(int dtype, const void* x, const void* dz, float* part, int N, int H, int W, int C,
+                                  long xps, int KH, int KW, int S, int P, int OH, int OW, long zps, void* stream) {
+  if (KH != 7 || !dmy_dwconv_ok(dtype, x, part, dz, N, H, W, C, C, C, xps, KH, KW, S, P, OH, OW, zps)) return -1;
+  hipStream_t st = (hipStream_t)stream;
+  const long RL = ((long)KH * KW + 1) * C;
+  return dtype ? launch_wgrad<bf16>(x, dz, part, RL, 1, N, H, W, C, xps, KH, S, OH, OW, zps, st)
+               : launch_wgrad<float>(x, dz, part, RL, 1, N, H, W, C, xps, KH, S, OH, OW, zps, st);
 }
 
 DMY_API int dmy_dwconv_wgrad_finalize(const float* part, int rows, int C, int KH, int KW, float* dw, int accumulate,
                                       void* stream) {
   if (rows < 1 || C < 1 || KH < 1 || KW < 1) return -1;
   const int KK = KH * KW;
-  dw_wgrad_finalize_kernel<<<ceil_div((long)KK * C, 256), 256, 0, (hipStream_t)stream>>>(part, rows, C, KK, dw,
-                                                                                        accumulate);
+  dw_wgrad_finalize_kernel<<<ceil_div((long)KK * C, 256), 256, 0, (hipStream_t)stream>>>(part, rows, C, KK, (long)KK * C,
+                                                                                        dw, accumulate, nullptr, 0);
+  return (int)hipGetLastError();
+}
+
+DMY_API int dmy_dwconv_wgrad_bias_finalize(const float* part, int rows, int C, int KH, int KW, float* dw, int accumulate,
+                                           float* dbias, int bias_accumulate, void* stream) {
+  if (rows < 1 || C < 1 || KH < 1 || KW < 1 || !dbias) return -1;
+  const int KK = KH * KW;
+  dw_wgrad_finalize_kernel<<<ceil_div((long)(KK + 1) * C, 256), 256, 0, (hipStream_t)stream>>>(
+      part, rows, C, KK, (long)(KK + 1) * C, dw, accumulate, dbias, bias_accumulate);
   return (int)hipGetLastError();
 }

@@ -50,6 +50,8 @@ SIGNATURES = {
     'dmy_dwconv_wgrad_rows': [L, I],
     'dmy_dwconv_wgrad': [I, P, P, P, I, I, I, I, L, I, I, I, I, I, I, L, P],
     'dmy_dwconv_wgrad_finalize': [P, I, I, I, I, P, I, P],
+    'dmy_dwconv_wgrad_bias': [I, P, P, P, I, I, I, I, L, I, I, I, I, I, I, L, P],
+    'dmy_dwconv_wgrad_bias_finalize': [P, I, I, I, I, P, I, P, I, P],
     # adapt.hip
     'dmy_adapt_gate_blocks': [I, L, I, I],
     'dmy_adapt_gate_fwd': [I, I, P, L, I, P, L, I, P, L, I, P, L, P, P, P, L, P, L, P],

@@ -672,7 +672,7 @@ def _dw_operands(x, weight, spec, need_grad, infer, wkey):
     x, xps = pixel_stride(x)
     N, C, H, W = x.shape
     OH, OW = conv_out_hw(H, W, k, s, p)
-    if OH < 1 or OW < 1 or C % VW[x.dtype] or p != k // 2 or k not in (3, 5) or s not in (1, 2):
+    if OH < 1 or OW < 1 or C % VW[x.dtype] or p != k // 2 or (k, s) not in ((3, 1), (3, 2), (5, 1), (5, 2), (7, 1)):
         raise _dw_unsupported(G, C, K, k, s, p)
     g = ConvGeom(N, C, H, W, xps, K, k, s, p, OH, OW, N * OH * OW, C, H, W, k, s, p, C, 0, G)
     w = spec.wcache[1] if infer and spec.wcache is not None and spec.wcache[0] == wkey else None
@@ -885,9 +885,16 @@ def _bwd1x1(ctx, dy, dps, x, wt, z, stats, coef):
     return sink_result(ctx.xsink, buf), dw
 
 
-def _act_bias_bwd(ctx, dt, dy, dps, z):
+def _dw_bias_in_wgrad(ctx):
+    """a biased 7x7 depthwise layer without BN (get_dwconv, models/common.py:1361-1362): its weight-grad launch carries
+    the bias gradient as one more partial row set (dmy_dwconv_wgrad_bias), so dz is not read a second time for it"""
+    return ctx.g.groups != 1 and ctx.g.k == 7 and ctx.has_bias and ctx.spec.bn is None and ctx.needs_input_grad[1]
+
+
+def _act_bias_bwd(ctx, dt, dy, dps, z, want_bias=True):
     """layer without BN -> (dz, its pixel stride, dbias): the activation's backward (dmy_bn_bwd_apply with the identity
-    affine map; dz is dy itself behind ACT_NONE) and the bias gradient, the column sums of dz"""
+    affine map; dz is dy itself behind ACT_NONE) and the bias gradient, the column sums of dz (None without a bias, or
+    with want_bias off: the weight-grad launch produces it, see _dw_bias_in_wgrad)"""
     K, M, dev = ctx.g.K, ctx.g.M, dy.device
     dz, dzps, dbias = dy, dps, None
     if ctx.spd:  # the same pass also undoes the SM fold, so it runs behind ACT_NONE too
@@ -900,7 +907,7 @@ def _act_bias_bwd(ctx, dt, dy, dps, z):
         zero, one = const_vec(K, 0.0, dev), const_vec(K, 1.0, dev)
         call('dmy_bn_bwd_apply', dt, ptr(z), K, ptr(dy), dps, ptr(one), ptr(zero), ptr(zero), ptr(one),
              ctx.spec.act, ptr(one), ptr(zero), ptr(zero), ptr(dz), K, M, K, stream())
-    if ctx.has_bias:
+    if ctx.has_bias and want_bias:
         P = call('dmy_bn_reduce_rows', dt, ptr(dz), dzps, None, 0, M, K)
         ps_, pq_ = f32(P * K, dev), f32(P * K, dev)
         call('dmy_bn_stats', dt, ptr(dz), dzps, M, K, ptr(ps_), ptr(pq_), stream())
@@ -928,8 +935,9 @@ def _dgrad(ctx, dt, dz, dzps, wt, z):
     return sink_result(ctx.xsink, buf)
 
 
-def _conv_wgrad(ctx, dt, x, dz, dzps):
-    """the weight gradient in torch OIHW order, in the weight's arena slice when it has one"""
+def _conv_wgrad(ctx, dt, x, dz, dzps, with_bias=False):
+    """-> (dw, dbias): the weight gradient in torch OIHW order, in the weight's arena slice when it has one; dbias is
+    None unless with_bias (_dw_bias_in_wgrad: the launch also sums dz per channel)"""
     g = ctx.g
     K, C, k, dev = g.K, g.C, g.k, dz.device
     if g.groups != 1:
@@ -938,12 +946,20 @@ def _conv_wgrad(ctx, dt, x, dz, dzps):
         dw, zeroed = _wgrad_target(ctx, (K, 1, k, k), dev)
         _dw_check(dt, x, dz, dz, g, g.xps, dzps)
         P = call('dmy_dwconv_wgrad_rows', g.M, C)
+        if with_bias:  # rows of (k * k + 1) * C: the bias gradient's share follows the filter taps
+            part, dbias = f32(P * (k * k + 1) * C, dev), _pgrad(ctx, 0, K, dev)
+            KernelTimer.run('dwconv_wgrad', g.flops(), 'dmy_dwconv_wgrad_bias', dt, ptr(x), ptr(dz), ptr(part), *g.dw(),
+                            dzps, stream(), tag=g.tag(),
+                            nbytes=x.element_size() * (g.N * g.H * g.W * C + g.M * C) + 4 * (k * k + 1) * C)
+            call('dmy_dwconv_wgrad_bias_finalize', ptr(part), P, C, k, k, ptr(dw), int(zeroed), ptr(dbias), 0,
+                 stream())
+            return dw, dbias
         part = f32(P * k * k * C, dev)
         KernelTimer.run('dwconv_wgrad', g.flops(), 'dmy_dwconv_wgrad', dt, ptr(x), ptr(dz), ptr(part), *g.dw(), dzps,
                         stream(), tag=g.tag(),
                         nbytes=x.element_size() * (g.N * g.H * g.W * C + g.M * C) + 4 * k * k * C)
         call('dmy_dwconv_wgrad_finalize', ptr(part), P, C, k, k, ptr(dw), int(zeroed), stream())
-        return dw
+        return dw, None
     dw, zeroed = _wgrad_target(ctx, (K, C, k, k), dev)
     if g.s2d:
         dwo = f32(K * 9 * g.s2d, dev)
@@ -958,7 +974,7 @@ def _conv_wgrad(ctx, dt, x, dz, dzps):
         dwo = f32(K * g.Cp * k * k, dev)
         _wgrad(dt, x, dz, dzps, dwo, g, 0)
         call('dmy_conv_wgrad_to_oihw', ptr(dwo), ptr(dw), K, C, g.Cp, k, k, stream())
-    return dw
+    return dw, None
 
 
 class ConvBNActFn(torch.autograd.Function):
@@ -1014,6 +1030,7 @@ class ConvBNActFn(torch.autograd.Function):
         if ctx.spd and (dps % VW[dy.dtype] or dy.data_ptr() % 16):  # the SM passes read dy as 16-byte vectors
             dy, dps = pixel_stride(dy.contiguous(memory_format=CL))
         dbias = dgamma = dbeta = fused = None
+        bias_in_wgrad = _dw_bias_in_wgrad(ctx)
         if spec.bn is not None:
             *stats, gamma = bnt
             *coef, dgamma, dbeta = _bn_bwd_coef(ctx, dt, dy, dps, z, stats, gamma)
@@ -1029,12 +1046,15 @@ class ConvBNActFn(torch.autograd.Function):
             if ctx.has_bias and ctx.train_bn:
                 dbias = _pgrad(ctx, 0, K, dev, zero=True)  # sum(dz) == 0 exactly behind train-mode BN
         else:
-            dz, dzps, dbias = _act_bias_bwd(ctx, dt, dy, dps, z)
+            dz, dzps, dbias = _act_bias_bwd(ctx, dt, dy, dps, z, want_bias=not bias_in_wgrad)
         if fused is not None:
             dx, dw = fused
         else:
             dx = _dgrad(ctx, dt, dz, dzps, wt, z) if ctx.needs_input_grad[0] else None
-            dw = _conv_wgrad(ctx, dt, x, dz, dzps) if ctx.needs_input_grad[1] else None
+            dw = None
+            if ctx.needs_input_grad[1]:
+                dw, db = _conv_wgrad(ctx, dt, x, dz, dzps, bias_in_wgrad)
+                dbias = db if bias_in_wgrad else dbias
         dres = (dy if ctx.rsink is None else ctx.rsink.passthrough(dy)) if ctx.has_res else None
         return dx, dw, dbias, dgamma, dbeta, dres, None, None, None, None, None, None
 
@@ -2006,3 +2026,4 @@ class AdaptAddFn(torch.autograd.Function):
         call('dmy_bifpn_wgrad', ptr(part), nb, n, ptr(wc), ctx.eps, ptr(dw), stream())
         grads = [sink_result(sinks[i], tg[i][0]) for i in range(n)]
         return (dw, None, None, *grads)
+

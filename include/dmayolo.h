@@ -140,8 +140,9 @@ int dmy_conv_wgrad_to_oihw(const float* dw_ohwi, float* dw_oihw, int K, int C, i
  *      channels: streaming kernels over NHWC, fp32 accumulation, no atomics (run-to-run bit-identical).
  *      w is the filter tap-major, channel-minor [KH][KW][C] in the activation dtype: exactly the IHWO copy
  *      dmy_conv_wprep / dmy_conv_wprep_multi write for a (C, 1, k, k) OIHW weight (K = C, C = 1).
+ *      Also nn.Conv2d(dim, dim, 7, padding=3, bias=True, groups=dim) of get_dwconv in GnConv (:1329, 1361-1362).
  *      dmy_dwconv_ok (models/common.py:79-82): 1 when the layer is supported -- groups == C == K, square k in
- *      {3, 5}, stride 1 or 2, padding k / 2, OH / OW the conv's output size, C a whole number of 16-byte vectors
+ *      {3, 5} with stride 1 or 2 or k = 7 with stride 1, padding k / 2, OH / OW the conv's output size, C a whole number of 16-byte vectors
  *      (C % 8 bf16, C % 4 fp32), pixel strides >= C and whole vectors, 16-byte aligned bases.  Every other entry
  *      returns -1 and launches nothing when its arguments fail that test. */
 int dmy_dwconv_ok(int dtype, const void* x, const void* w, const void* z, int N, int H, int W, int C, int K, int groups,
@@ -169,6 +170,14 @@ int dmy_dwconv_wgrad(int dtype, const void* x, const void* dz, float* part, int 
                      int KW, int S, int P, int OH, int OW, long zps, void* stream);
 int dmy_dwconv_wgrad_finalize(const float* part, int rows, int C, int KH, int KW, float* dw, int accumulate,
                               void* stream);
+/* backward of get_dwconv(dim, 7, True) (models/common.py:1361-1362) w.r.t. weight and bias in one launch, k = 7 only
+ * (-1 otherwise): the same dmy_dwconv_wgrad_rows(M, C) partial rows, each [(KH * KW + 1) * C], whose last C floats are
+ * the row's share of the bias gradient sum_pixels dz.  dmy_dwconv_wgrad_bias_finalize sums them in row order into dw
+ * as above and into dbias = (bias_accumulate ? dbias : 0) + sum.  No atomics: both are run-to-run bit-identical. */
+int dmy_dwconv_wgrad_bias(int dtype, const void* x, const void* dz, float* part, int N, int H, int W, int C, long xps,
+                          int KH, int KW, int S, int P, int OH, int OW, long zps, void* stream);
+int dmy_dwconv_wgrad_bias_finalize(const float* part, int rows, int C, int KH, int KW, float* dw, int accumulate,
+                                   float* dbias, int bias_accumulate, void* stream);
 
 /* ---- adaptive-fusion necks (csrc/adapt.hip): AdaptConcat (models/common.py:953-992) and Adapt_Add2 / Adapt_Add3
  *      (models/common.py:1028-1061).  Streaming NHWC kernels, fp32 arithmetic, no atomics (run-to-run bit-identical).
