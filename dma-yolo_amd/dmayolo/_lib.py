@@ -97,6 +97,12 @@ SIGNATURES = {
     'dmy_maxpool2_bwd': [I, P, L, P, P, L, I, I, I, I, I, P],
     'dmy_spd_split_fwd': [I, P, L, P, L, P, L, P, I, I, I, I, P],
     'dmy_spd_split_bwd': [I, P, L, P, L, P, P, L, I, I, I, I, P],
+    # hor.hip
+    'dmy_gate_fwd': [I, P, L, P, L, P, L, L, I, F, P],
+    'dmy_gate_bwd': [I, P, L, P, L, P, L, P, L, P, L, L, I, F, P],
+    'dmy_layerscale_fwd': [I, P, L, P, P, P, L, L, I, P],
+    'dmy_layerscale_bwd_rows': [L],
+    'dmy_layerscale_bwd': [I, P, L, P, P, P, L, I, P, P],
     # eltwise.hip
     'dmy_maxpool_fwd': [I, P, L, P, L, P, I, I, I, I, I, P],
     'dmy_maxpool_chain3_fwd': [I, P, L, P, P, P, L, I, I, I, I, I, P],

@@ -2027,3 +2027,179 @@ class AdaptAddFn(torch.autograd.Function):
         grads = [sink_result(sinks[i], tg[i][0]) for i in range(n)]
         return (dw, None, None, *grads)
 
+
+
+# ------------------------------------------------------------------ GnConv / HorBlock (csrc/hor.hip)
+
+class SliceSink:
+    """Gradient buffer of an activation that is only read through channel slices (torch.split, models/common.py:1347,
+    1351).  The consumers' backward kernels write their slice's gradient straight into this one NHWC buffer through
+    `part(c0, C)`, which follows the GradSink protocol (target / peek / done / passthrough), and the n-th SplitFn
+    backward hands the finished buffer to autograd (the others return None): no zero-filled slice gradients, no adds.
+    The slices must cover every channel.  Resets after the n-th contribution, like GradSink."""
+    __slots__ = ('n', 'seen', 'buf', 'shape', 'dtype', 'device')
+
+    def __init__(self, n, like):
+        self.n, self.seen, self.buf = n, 0, None
+        self.shape, self.dtype, self.device = tuple(like.shape), like.dtype, like.device
+
+    def view(self, c0, C):
+        if self.buf is None:
+            self.buf = torch.empty(self.shape, dtype=self.dtype, device=self.device, memory_format=CL)
+        return self.buf[:, c0:c0 + C]
+
+    def part(self, c0, C):
+        return _SlicePart(self, c0, C)
+
+    def tick(self):
+        self.seen += 1
+        if self.seen < self.n:
+            return None
+        ret = self.buf
+        self.buf, self.seen = None, 0
+        return ret
+
+
+class _SlicePart:
+    """one channel slice of a SliceSink as a kernel's gradient target: always written, never accumulated; the slice
+    view is what the backward returns, and SplitFn.backward recognises it as already in place"""
+    __slots__ = ('sink', 'c0', 'C')
+
+    def __init__(self, sink, c0, C):
+        self.sink, self.c0, self.C = sink, c0, C
+
+    def target(self, N, C, H, W, like):
+        return self.sink.view(self.c0, self.C), self.sink.shape[1], 0
+
+    def peek(self, N, C, H, W):
+        return self.sink.view(self.c0, self.C), self.sink.shape[1]
+
+    def done(self):
+        return self.sink.view(self.c0, self.C)
+
+    def passthrough(self, g):
+        g, gps = pixel_stride(g)
+        v = self.sink.view(self.c0, self.C)
+        N, C, H, W = g.shape
+        call('dmy_slice_copy', dcode(g), ptr(g), gps, ptr(v), self.sink.shape[1], N * H * W, C, None, 0, 0, 0.0, 0,
+             stream())
+        return v
+
+
+class SplitFn(torch.autograd.Function):
+    """x[:, c0:c0 + C] as a view (one output of torch.split); the gradient goes into `sink` (a SliceSink over x's
+    channels, or None: a zero-filled gradient with the slice copied in)."""
+
+    @staticmethod
+    def forward(ctx, x, c0, C, sink=None):
+        ctx.c0, ctx.C, ctx.sink, ctx.xshape = c0, C, sink, tuple(x.shape)
+        return x[:, c0:c0 + C]
+
+    @staticmethod
+    def backward(ctx, g):
+        sink = ctx.sink
+        if sink is None:
+            sink = SliceSink(1, torch.empty(ctx.xshape, dtype=g.dtype, device='meta'))
+            sink.device = g.device
+            sink.view(0, ctx.xshape[1]).zero_()
+        v = sink.view(ctx.c0, ctx.C)
+        if g.data_ptr() != v.data_ptr() or g.stride() != v.stride() or g.dtype != v.dtype:
+            _SlicePart(sink, ctx.c0, ctx.C).passthrough(g.to(v.dtype))
+        return sink.tick(), None, None, None
+
+
+def _hor_check(what, dtype, C, strides, tensors):
+    """the hor.hip kernels move whole 16-byte vectors (as _adapt_check)"""
+    vw = VW[dtype]
+    if C % vw or any(s % vw for s in strides) or any(t.data_ptr() % 16 for t in tensors):
+        raise NotImplementedError(f'{what}: {C} channels / pixel strides {list(strides)} must be multiples of {vw} for '
+                                  f'{dtype} and every tensor 16-byte aligned')
+
+
+def _write_target(sink, N, C, H, W, like):
+    """-> (buffer, pixel stride, finish) for a backward kernel that writes but cannot accumulate: the sink's buffer
+    when this is its first contribution (or a SliceSink part), else a fresh tensor that finish() adds into the sink"""
+    buf, ps, acc = sink_target(sink, N, C, H, W, like)
+    if not acc:
+        return buf, ps, lambda: sink_result(sink, buf)
+    tmp = new_act(N, C, H, W, like)
+    return tmp, C, lambda: sink.passthrough(tmp)
+
+
+class GateMulFn(torch.autograd.Function):
+    """y = a * b * scale: GnConv's gates `pwa * dw_list[0]`, `pws[i](x) * dw_list[i + 1]` with dw_abc's `* self.scale`
+    (models/common.py:1349-1355).  a and b may be channel slices of wider buffers; the backward writes da / db in one
+    launch into asink / bsink's targets (SliceSink parts: the slices of d(fused_x) / d(dw_abc))."""
+
+    @staticmethod
+    def forward(ctx, a, b, scale, asink=None, bsink=None, out=None):
+        """out: None or [view] -- see out_view"""
+        a, aps = pixel_stride(a)
+        b, bps = pixel_stride(b)
+        if a.shape != b.shape or a.dtype != b.dtype:
+            raise ValueError(f'GateMulFn: operands {tuple(a.shape)} {a.dtype} and {tuple(b.shape)} {b.dtype}')
+        N, C, H, W = a.shape
+        y, yps = out_view(out and out[0], a.shape, a)
+        if y is None:
+            y, yps = new_act(N, C, H, W, a), C
+        _hor_check('GateMulFn', a.dtype, C, [aps, bps, yps], [a, b, y])
+        call('dmy_gate_fwd', dcode(a), ptr(a), aps, ptr(b), bps, ptr(y), yps, N * H * W, C, float(scale), stream())
+        ctx.save_for_backward(a, b)
+        ctx.ps, ctx.scale, ctx.asink, ctx.bsink = (aps, bps), float(scale), asink, bsink
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        a, b = ctx.saved_tensors
+        aps, bps = ctx.ps
+        N, C, H, W = a.shape
+        dy, dps = pixel_stride(dy.to(a.dtype))
+        da, daps, fa = _write_target(ctx.asink, N, C, H, W, a)
+        db, dbps, fb = _write_target(ctx.bsink, N, C, H, W, a)
+        _hor_check('GateMulFn backward', a.dtype, C, [dps, daps, dbps], [dy, da, db])
+        call('dmy_gate_bwd', dcode(a), ptr(dy), dps, ptr(a), aps, ptr(b), bps, ptr(da), daps, ptr(db), dbps, N * H * W,
+             C, ctx.scale, stream())
+        return fa(), fb(), None, None, None, None
+
+
+class LayerScaleAddFn(torch.autograd.Function):
+    """out = x + gamma[c] * y: HorBlock's layer-scaled residuals (models/common.py:1388, 1395-1398, no DropPath).  The
+    backward is one launch for dy = gamma * dout and the partial rows of dgamma = sum_m dout * y (summed in row order
+    by dmy_reduce_rows); dx is dout itself, handed to xsink as a passthrough."""
+
+    @staticmethod
+    def forward(ctx, x, y, gamma, xsink=None, out=None):
+        """out: None or [view] -- see out_view"""
+        x, xps = pixel_stride(x)
+        y = y.contiguous(memory_format=CL)
+        N, C, H, W = x.shape
+        if y.shape != x.shape or y.dtype != x.dtype or gamma.dtype != torch.float32 or gamma.numel() != C:
+            raise ValueError(f'LayerScaleAddFn: x {tuple(x.shape)} {x.dtype}, y {tuple(y.shape)} {y.dtype}, gamma '
+                             f'{tuple(gamma.shape)} {gamma.dtype}')
+        gm = gamma.detach().contiguous()
+        o, ops = out_view(out and out[0], x.shape, x)
+        if o is None:
+            o, ops = new_act(N, C, H, W, x), C
+        _hor_check('LayerScaleAddFn', x.dtype, C, [xps, ops], [x, y, o])
+        call('dmy_layerscale_fwd', dcode(x), ptr(x), xps, ptr(y), ptr(gm), ptr(o), ops, N * H * W, C, stream())
+        ctx.save_for_backward(y, gm)
+        ctx.xsink = xsink
+        return o
+
+    @staticmethod
+    def backward(ctx, dout):
+        y, gm = ctx.saved_tensors
+        N, C, H, W = y.shape
+        M, dev = N * H * W, y.device
+        dout, dps = pixel_stride(dout.to(y.dtype))
+        _hor_check('LayerScaleAddFn backward', y.dtype, C, [dps], [dout])
+        if C // VW[y.dtype] > 256:
+            raise NotImplementedError(f'LayerScaleAddFn backward: {C} channels, at most {256 * VW[y.dtype]}')
+        dy = new_act(N, C, H, W, y)
+        P = call('dmy_layerscale_bwd_rows', M)
+        part = f32(P * C, dev)
+        call('dmy_layerscale_bwd', dcode(y), ptr(dout), dps, ptr(y), ptr(gm), ptr(dy), M, C, ptr(part), stream())
+        dgamma = f32(C, dev)
+        call('dmy_reduce_rows', ptr(part), P, C, ptr(dgamma), 0, stream())
+        dx = dout if ctx.xsink is None else ctx.xsink.passthrough(dout)
+        return dx, dy, dgamma, None, None

@@ -21,7 +21,7 @@ __all__ = ['autopad', 'Conv', 'DWConv', 'GhostConv', 'GhostBottleneck', 'C3Ghost
            'CABottleneck', 'C3CA', 'Concat', 'AdConcat2', 'AdConcat3', 'AdaptConcat', 'Adapt_Add2', 'Adapt_Add3', 'AdaptADD',
            'Upsample', 'C3STR', 'SwinTransformerBlock',
            'SwinTransformerLayer', 'WindowAttention', 'Mlp', 'DropPath', 'space_to_depth', 'SM', 'MP', 'DMConv', 'DMMConv',
-           'DMMConv2', 'SPP', 'CBAM',
+           'DMMConv2', 'SPP', 'CBAM', 'LayerNorm', 'GnConv', 'HorBlock', 'C3HB',
            'ChannelAttentionModule', 'SpatialAttentionModule', 'C3TR', 'TransformerBlock', 'TransformerLayer']
 
 
@@ -741,6 +741,136 @@ class C3STR(C3):
         super().__init__(c1, c2, n, shortcut, g, e)
         c_ = int(c2 * e)
         self.m = SwinTransformerBlock(c_, c_, c_ // 32, n)
+
+
+# ------------------------------------------------------------------ HorNet: GnConv / HorBlock / C3HB (csrc/hor.hip)
+
+class LayerNorm(nn.Module):
+    """models/common.py:1402-1427.  Activations here are NHWC whatever the reference's layout at that point, so both
+    data formats are Fn.LayerNormFn over the channels (the channels_first formula is the same biased-variance norm)."""
+
+    def __init__(self, normalized_shape, eps=1e-6, data_format='channels_last'):
+        super().__init__()
+        self.weight = nn.Parameter(torch.ones(normalized_shape))
+        self.bias = nn.Parameter(torch.zeros(normalized_shape))
+        self.eps = eps
+        self.data_format = data_format
+        if self.data_format not in ['channels_last', 'channels_first']:
+            raise NotImplementedError
+        self.normalized_shape = (normalized_shape,)
+
+    def forward(self, x, sink=None):
+        return Fn.LayerNormFn.apply(x, self.weight, self.bias, self.eps, sink)
+
+
+class GnConv(nn.Module):
+    """Recursive gated convolution, models/common.py:1318-1359.  proj_in writes one 2 * c1-channel buffer; the biased
+    depthwise 7x7 reads its abc slice in place (pixel stride 2 * c1) and the gates read pwa and the dw_list slices
+    through Fn.SplitFn views, so torch.split copies nothing; in the backward every gate writes its slice of d(dw_abc) /
+    d(fused_x) directly (Fn.SliceSink).  `scale` is applied by the gate kernel."""
+
+    def __init__(self, c1, c2, ksize=1, stride=1, order=5, gflayer=None, h=14, w=8, s=1.0):
+        super().__init__()
+        if gflayer is not None:
+            raise NotImplementedError('GnConv: gflayer (the global-filter depthwise layer) has no gfx950 kernel')
+        self.order = order
+        self.dims = [c1 // 2 ** i for i in range(order)]
+        self.dims.reverse()
+        self.proj_in = nn.Conv2d(c1, 2 * c1, 1)
+        sd = sum(self.dims)
+        self.dwconv = nn.Conv2d(sd, sd, kernel_size=7, padding=3, bias=True, groups=sd)  # get_dwconv(sd, 7, True)
+        self.proj_out = Conv(c1, c2, ksize, stride)
+        self.pws = nn.ModuleList([nn.Conv2d(self.dims[i], self.dims[i + 1], 1) for i in range(order - 1)])
+        self.scale = s
+
+    def _check(self, x):
+        """every gate operand is a whole number of 16-byte vectors at a vector offset of its buffer"""
+        c1 = self.proj_in.in_channels
+        vw = Fn.VW.get(x.dtype)
+        if vw is None or c1 % 2 ** (self.order - 1) or any(d % vw for d in self.dims):
+            raise NotImplementedError(f'GnConv: c1={c1} gives the gate widths {self.dims}, which must be multiples of '
+                                      f'{vw} channels for {x.dtype} (c1 >= {16 * (vw or 0)} at order 5)')
+
+    def forward(self, x, mask=None, dummy=False, res=None, rsink=None, out=None):
+        """res / rsink / out: proj_out's residual, its GradSink and a concat_buffer slice, as Conv.forward"""
+        self._check(x)
+        dims, sd = self.dims, sum(self.dims)
+        fused = conv_forward(self.proj_in, None, None, x)
+        grad = torch.is_grad_enabled()
+        sf = Fn.SliceSink(2, fused) if grad else None  # d(fused_x): pwa's slice from gate 0, abc's from the dwconv
+        pwa = Fn.SplitFn.apply(fused, 0, dims[0], sf)
+        abc = Fn.SplitFn.apply(fused, dims[0], sd, sf)
+        dw = conv_forward(self.dwconv, None, None, abc, xsink=sf.part(dims[0], sd) if grad else None)
+        sw = Fn.SliceSink(self.order, dw) if grad else None  # d(dw_abc): one slice per gate
+        a, c0 = pwa, 0
+        for i, d in enumerate(dims):
+            if i:
+                a = conv_forward(self.pws[i - 1], None, None, a)
+            a = Fn.GateMulFn.apply(a, Fn.SplitFn.apply(dw, c0, d, sw), self.scale,
+                                   sf.part(0, d) if grad and i == 0 else None, sw.part(c0, d) if grad else None)
+            c0 += d
+        return self.proj_out(a, res=res, rsink=rsink, out=out)
+
+
+class HorBlock(nn.Module):
+    """models/common.py:1364-1400: x + gamma1 * gnconv(norm1(x)), then x + gamma2 * pwconv2(gelu(pwconv1(norm2(x)))).
+    As in the reference the block builds GnConv(dim, dim) whatever `gnconv` names."""
+
+    dmy_out = True  # forward(x, out=view) writes its result into a concat_buffer slice when it can (C3.forward)
+
+    def __init__(self, dim, drop_path=0., layer_scale_init_value=1e-6, gnconv=GnConv):
+        super().__init__()
+        if drop_path > 0.:
+            raise NotImplementedError('HorBlock: drop_path > 0 has no gfx950 path (no YAML reaches it)')
+        self.norm1 = LayerNorm(dim, eps=1e-6, data_format='channels_first')
+        self.gnconv = GnConv(dim, dim)
+        self.norm2 = LayerNorm(dim, eps=1e-6)
+        self.pwconv1 = nn.Linear(dim, 4 * dim)
+        self.act = nn.GELU()
+        self.pwconv2 = nn.Linear(4 * dim, dim)
+        self.gamma1 = nn.Parameter(layer_scale_init_value * torch.ones(dim),
+                                   requires_grad=True) if layer_scale_init_value > 0 else None
+        self.gamma2 = nn.Parameter(layer_scale_init_value * torch.ones((dim)),
+                                   requires_grad=True) if layer_scale_init_value > 0 else None
+        self.drop_path = nn.Identity()
+
+    def forward(self, x, out=None):
+        """out: a concat_buffer slice the second residual sum is written into (C3HB's last block)"""
+        c = x.shape[1]
+        self.gnconv._check(x)
+        s1, s2 = Fn.GradSink(2), Fn.GradSink(2)  # x -> norm1 + residual; x2 -> norm2 + residual
+        u = self.norm1(x, s1)
+        if self.gamma1 is None:
+            x = self.gnconv(u, res=x, rsink=s1)
+        else:
+            x = Fn.LayerScaleAddFn.apply(x, self.gnconv(u), self.gamma1, s1)
+        u2 = self.norm2(x, s2)
+        h = Fn.conv_bn_act(u2, self.pwconv1.weight.view(4 * c, c, 1, 1), self.pwconv1.bias, None, 1, 0, Fn.ACT_GELU)
+        w2, b2 = self.pwconv2.weight.view(c, 4 * c, 1, 1), self.pwconv2.bias
+        if self.gamma2 is None:
+            return Fn.conv_bn_act(h, w2, b2, None, 1, 0, Fn.ACT_NONE, res=x, rsink=s2, out=out)
+        return Fn.LayerScaleAddFn.apply(x, Fn.conv_bn_act(h, w2, b2, None, 1, 0, Fn.ACT_NONE), self.gamma2, s2,
+                                        [out] if out is not None else None)
+
+
+class _HorStack(nn.Sequential):
+    """C3HB.m: the HorBlocks in sequence, the last one writing into C3's concat buffer"""
+    dmy_out = True
+
+    def forward(self, x, out=None):
+        blocks = list(self)
+        for b in blocks[:-1]:
+            x = b(x)
+        return blocks[-1](x, out=out) if blocks else x
+
+
+class C3HB(C3):
+    """models/common.py:1429-1439: C3 whose bottleneck stack is n HorBlock(c_)."""
+
+    def __init__(self, c1, c2, n=1, shortcut=True, g=1, e=0.5):
+        super().__init__(c1, c2, n, shortcut, g, e)
+        c_ = int(c2 * e)
+        self.m = _HorStack(*(HorBlock(c_) for _ in range(n)))
 
 
 # ------------------------------------------------------------------ C3TR (config 5: global MHSA over P5 tokens)

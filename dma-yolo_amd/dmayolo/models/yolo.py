@@ -20,7 +20,7 @@ import torch.nn as nn
 from .. import functional as Fn
 from ..functional import call, ptr, stream, dcode
 from .common import *  # noqa: F401,F403  (the YAML namespace)
-from .common import Conv, Upsample, SCConv, GhostConv, GhostBottleneck, autopad, space_to_depth, MP, DMConv, DMMConv, DMMConv2
+from .common import Conv, Upsample, SCConv, GhostConv, GhostBottleneck, autopad, space_to_depth, MP, DMConv, DMMConv, DMMConv2, GnConv
 from .tdetect import TDetect
 from ..utils.general import make_divisible
 from ..utils.torch_utils import initialize_weights, fuse_conv_and_bn
@@ -121,6 +121,8 @@ def _out_hw(m, hw):
         return ((hw[0] + 2 * p - k) // s + 1, (hw[1] + 2 * p - k) // s + 1)
     if isinstance(m, GhostBottleneck):
         return _out_hw(m.conv[1], hw)  # the stride-2 DWConv, or the Identity placeholder
+    if isinstance(m, GnConv):  # proj_in, the depthwise 7x7 and the gates keep the map; HorBlock and C3HB keep it too
+        return _out_hw(m.proj_out, hw)
     if isinstance(m, SCConv):
         s = m.k4[0].stride[0]
         return ((hw[0] - 1) // s + 1, (hw[1] - 1) // s + 1)
@@ -514,8 +516,8 @@ def parse_model(d, ch):
     no = na * (nc + 5)
     ev = dict(ns, nc=nc, anchors=anchors)
     chan_mods = (C.Conv, C.DWConv, C.GhostConv, C.GhostBottleneck, C.C3Ghost, C.Bottleneck, C.SPPF, C.C3, C.C3TR, C.C3STR, C.CoorAttention, C.CABottleneck, C.C3CA,
-                 C.SPPFCSPC, C.SCConv, C.SPP, C.CBAM)
-    rep_mods = (C.C3, C.C3TR, C.C3STR, C.C3CA, C.C3Ghost)
+                 C.SPPFCSPC, C.SCConv, C.SPP, C.CBAM, C.C3HB, C.HorBlock, C.GnConv)
+    rep_mods = (C.C3, C.C3TR, C.C3STR, C.C3CA, C.C3Ghost, C.C3HB)
     layers, save, c2 = [], [], ch[-1]
     for i, (f, n, m, args) in enumerate(d['backbone'] + d['head']):
         m = eval(m, ev) if isinstance(m, str) else m

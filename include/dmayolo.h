@@ -300,6 +300,30 @@ int dmy_spd_split_fwd(int dtype, const void* x, long xps, void* sm, long smps, v
 int dmy_spd_split_bwd(int dtype, const void* dsm, long dsmps, const void* dmp, long dmpps, const unsigned char* argmax,
                       void* dx, long dxps, int N, int H, int W, int C, void* stream);
 
+/* ---- GnConv / HorBlock (csrc/hor.hip): the recursive gate product and the layer-scaled residual
+ *      (models/common.py:1343-1359, 1382-1400).  Streaming NHWC kernels over M pixels of C channels, fp32 arithmetic,
+ *      one rounding per stored element, no atomics.  Supported: C and every pixel stride a whole number of 16-byte
+ *      vectors (8 channels bf16, 4 fp32), pixel strides >= C, 16-byte aligned bases, so an operand may be a channel
+ *      slice of a wider buffer at a vector offset; anything else returns hipErrorInvalidValue and launches nothing. */
+/* models/common.py:1349-1355: `pwa * dw_list[0]` and `self.pws[i](x) * dw_list[i + 1]` with the `* self.scale` of
+ * dw_abc folded in: y = a * b * scale.  a, b, y each with their own pixel stride. */
+int dmy_gate_fwd(int dtype, const void* a, long aps, const void* b, long bps, void* y, long yps, long M, int C,
+                 float scale, void* stream);
+/* the backward of the same lines in one launch: da = dy * b * scale, db = dy * a * scale, each written (not
+ * accumulated) through its own pixel stride (torch.split's backward :1347, :1351 is the slice addressing). */
+int dmy_gate_bwd(int dtype, const void* dy, long dps, const void* a, long aps, const void* b, long bps, void* da,
+                 long daps, void* db, long dbps, long M, int C, float scale, void* stream);
+/* models/common.py:1388 and :1395-1398 without DropPath: out = x + gamma[c] * y.  x and out strided, y dense [M][C],
+ * gamma fp32 [C]. */
+int dmy_layerscale_fwd(int dtype, const void* x, long xps, const void* y, const float* gamma, void* out, long ops,
+                       long M, int C, void* stream);
+/* its backward in one launch: dy = gamma[c] * dout (dense [M][C]) and one partial row per block of sum_m dout * y,
+ * part [dmy_layerscale_bwd_rows(M)][C], every row written, for dmy_reduce_rows (-> dgamma, rows summed in row order:
+ * bit-identical run to run).  dx is dout itself.  At most 256 vectors per row. */
+int dmy_layerscale_bwd_rows(long M);
+int dmy_layerscale_bwd(int dtype, const void* dout, long dps, const void* y, const float* gamma, void* dy, long M,
+                       int C, float* part, void* stream);
+
 /* ---- memory-bound NHWC ops */
 /* nn.MaxPool2d(k, 1, k//2): SPPF common.py:250-258, SPPFCSPC :1266-1274 */
 int dmy_maxpool_fwd(int dtype, const void* x, long xps, void* y, long yps, unsigned char* argmax, int N, int H, int W,
