@@ -114,8 +114,8 @@ DEV float act_grad(int act, float u) {
       const float s = sigmoidf_(u);
       return s * (1.0f + u * (1.0f - s));
     }
-    case ACT_HARDSWISH:  // torch hardswish_backward: u<-3 -> 0, u<=3 -> u/3+0.5, else 1
-      return u < -3.0f ? 0.0f : (u <= 3.0f ? u / 3.0f + 0.5f : 1.0f);
+    case ACT_HARDSWISH:  // torch hardswish_backward: u<=-3 -> 0, u<3 -> u/3+0.5, else 1 (the kinks take the flat side)
+      return u <= -3.0f ? 0.0f : (u < 3.0f ? u / 3.0f + 0.5f : 1.0f);
     case ACT_SIGMOID: {
       const float s = sigmoidf_(u);
       return s * (1.0f - s);

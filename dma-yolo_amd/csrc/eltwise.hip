@@ -1092,8 +1092,9 @@ __global__ void ca_apply_bwd_att_kernel(const T* __restrict__ x, long xps, const
 template <typename S, typename T>
 __global__ void nchw_to_nhwc_kernel(const S* __restrict__ x, T* __restrict__ y, int N, int C, int H, int W, int Cp,
                                     float scale) {
-  // one thread per pixel: C plane reads (coalesced across threads along w), Cp contiguous writes
-  // (16-B vectors when Cp*sizeof(T) is a multiple of 16); channels [C, Cp) are zero (stem padding)
+  // one thread per pixel: C plane reads (coalesced across threads along w), Cp contiguous writes as 16-B vectors:
+  // Cp is a whole number of vectors and y is 16-B aligned (dmy_nchw_to_nhwc rejects anything else, since a pixel
+  // at i * Cp would otherwise start off a 16-B boundary); channels [C, Cp) are zero (stem padding)
   const long HW = (long)H * W, total = (long)N * HW;
   constexpr int VW = Traits<T>::VW;
   for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
@@ -1104,11 +1105,7 @@ __global__ void nchw_to_nhwc_kernel(const S* __restrict__ x, T* __restrict__ y, 
       float f[VW];
 #pragma unroll
       for (int j = 0; j < VW; ++j) f[j] = (c0 + j < C) ? (float)src[(long)(c0 + j) * HW] * scale : 0.f;
-      if (c0 + VW <= Cp) {
-        *reinterpret_cast<uint4*>(dst + c0) = pack<T>(f);
-      } else {
-        for (int j = 0; c0 + j < Cp; ++j) dst[c0 + j] = from_f<T>(f[j]);
-      }
+      *reinterpret_cast<uint4*>(dst + c0) = pack<T>(f);
     }
   }
 }
@@ -1611,9 +1608,12 @@ DMY_API int dmy_image_s2d(int dtype, int src_kind, const void* x, void* y, int N
   }
   return (int)hipGetLastError();
 }
-// src_kind: 0 = uint8, 1 = fp32; output NHWC with pixel stride Cp >= C (zero-filled tail channels)
+// src_kind: 0 = uint8, 1 = fp32; output NHWC with pixel stride Cp >= C (zero-filled tail channels).  Cp must be a
+// whole number of 16-B vectors of the storage type (functional.vec_pad) and y 16-B aligned: hipErrorInvalidValue
+// otherwise
 DMY_API int dmy_nchw_to_nhwc(int dtype, int src_kind, const void* x, void* y, int N, int C, int H, int W, int Cp,
                              float scale, void* stream) {
+  if (Cp % (dtype ? 8 : 4) || Cp < C || (((uintptr_t)y) & 15)) return (int)hipErrorInvalidValue;
   hipStream_t st = (hipStream_t)stream;
   const long n = (long)N * H * W;
   if (src_kind == 0) {

@@ -381,6 +381,8 @@ int dmy_ca_apply_bwd(int dtype, const void* x, long xps, const void* lh, const v
  * times scale (train.py:402 `/255`); the stem conv's input in its k3 s1 form */
 int dmy_image_s2d(int dtype, int src_kind, const void* x, void* y, int N, int C, int H, int W, int Cs, float scale,
                   void* stream);
+/* NCHW image -> NHWC [N][H][W][Cp] times scale, channels [C, Cp) zero; Cp a whole number of 16-byte vectors of the
+ * storage type (8 bf16 / 4 fp32), Cp >= C and y 16-byte aligned, hipErrorInvalidValue otherwise */
 int dmy_nchw_to_nhwc(int dtype, int src_kind, const void* x, void* y, int N, int C, int H, int W, int Cp, float scale,
                      void* stream);
 /* one test-time-augmentation input (models/yolo.py:199-201 with utils/torch_utils.py:264-274 scale_img): the NCHW
