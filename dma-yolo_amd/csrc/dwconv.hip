@@ -74,7 +74,7 @@ DEV Strip strip_of(long st, int OH, int SW) {
   return s;
 }
 
-enum { EPI_STATS = 0, EPI_ACT = 1, EPI_ACC = 2 };
+enum { EPI_STATS = 0, EPI_ACT = 1, EPI_ACC = 2, EPI_ACTBN = 3 };
 
 // out[n, oh, ow, c] = sum_ij in[n, oh * S - P + i, ow * S - P + j, c] * w[i][j][c], P = K / 2; FLIP reads w[K-1-i][K-1-j]
 // (the stride-1 data-grad is this correlation of dz with the flipped filter).
@@ -421,6 +421,215 @@ dw_wgrad_row_kernel(const T* __restrict__ x, const T* __restrict__ dz, float* __
   }
 }
 
+// ---------------------------------------------------------------- 9 x 9, stride 1, padding 4 (ConvMix, models/cspcm.py:29)
+// The K <= 7 kernels hold a whole filter row (K vectors) next to the kTW accumulators; at K = 7 in bf16 that already
+// takes every VGPR.  The 9 x 9 bodies load the filter per column instead: the input columns of a filter row are walked
+// once, column jj loads the one new filter vector w[i][jj] into a ring of kTW vectors (the taps jj - kTW + 1 .. jj are
+// all an output of the strip still needs), and the filter rows are a real loop, not unrolled code.  Live per thread:
+// kTW accumulators + kTW filter vectors + one input vector.  No LDS, no barrier in the main loop ("Depthwise
+// 9 x 9").  Bounds as above: rows out of range are skipped, columns clamped to column 0 and zeroed, stores predicated.
+//   EPI_STATS / EPI_ACT / EPI_ACC: as dw_conv_kernel
+//   EPI_ACTBN: y = act(T(acc + bias)) * scale + shift (+ res)     (scale / shift nullable together)
+// this block's row of the two [rows][C] partial arrays from the per-thread sums s1 / s2: lanes that share a channel unit
+// -> the four waves through LDS, summed in wave order.  Every thread of the block must call it.  The same
+// steps as the tail of dw_conv_kernel, which stays inline there: through this helper its bf16 instantiations compile to
+// one SGPR fewer, and their resource usage is pinned to what it was.
+template <int VW>
+DEV void write_stat_rows(const float* s1, const float* s2, int tcl, int C, float* __restrict__ psum,
+                         float* __restrict__ psq) {
+  __shared__ float red[4][2 * 32 * VW];
+  const int TC = 1 << tcl, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+  for (int e = 0; e < VW; ++e) {
+    const float a = unit_sum(s1[e], tcl), q = unit_sum(s2[e], tcl);
+    if (lane < TC) {
+      red[wave][lane * VW + e] = a;
+      red[wave][32 * VW + lane * VW + e] = q;
+    }
+  }
+  __syncthreads();
+  const int nch = TC * VW;
+  for (int idx = threadIdx.x; idx < 2 * nch; idx += 256) {
+    const int half = idx >= nch, cc = idx - half * nch, ch = blockIdx.y * nch + cc;
+    if (ch < C) {
+      const int o = half * 32 * VW + cc;
+      (half ? psq : psum)[(long)blockIdx.x * C + ch] = ((red[0][o] + red[1][o]) + red[2][o]) + red[3][o];
+    }
+  }
+}
+
+template <typename T, bool FLIP, int EPI>
+__global__ void __launch_bounds__(256)
+dw9_conv_kernel(const T* __restrict__ x, const T* __restrict__ w, const float* __restrict__ bias, T* __restrict__ y,
+                float* __restrict__ psum, float* __restrict__ psq, int N, int IH, int IW, int C, long ips, int OH, int OW,
+                long ops, int tcl, const float* __restrict__ scale, const float* __restrict__ shift, int act,
+                const T* __restrict__ res, long rps, int accumulate) {
+  constexpr int VW = Traits<T>::VW, K = 9, P = 4, NC = kTW - 1 + K;
+  const int TC = 1 << tcl, cu = threadIdx.x & (TC - 1), slot = threadIdx.x >> tcl, PIX = 256 >> tcl;
+  const int cv = blockIdx.y * TC + cu;
+  const bool cok = cv < C / VW;
+  const int c0 = cok ? cv * VW : 0;
+  const int SW = (OW + kTW - 1) / kTW;
+  const long nstrips = (long)N * OH * SW, ngroups = (nstrips + PIX - 1) / PIX;
+  float s1[VW], s2[VW], bs[VW], sc[VW], sh[VW];
+#pragma unroll
+  for (int e = 0; e < VW; ++e) { s1[e] = 0.f; s2[e] = 0.f; bs[e] = 0.f; sc[e] = 1.f; sh[e] = 0.f; }
+  if (EPI != EPI_ACC && bias && cok) ldf<VW>(bias + c0, bs);
+  if ((EPI == EPI_ACT || EPI == EPI_ACTBN) && scale && cok) {
+    ldf<VW>(scale + c0, sc);
+    ldf<VW>(shift + c0, sh);
+  }
+  for (long g = blockIdx.x; g < ngroups; g += gridDim.x) {
+    const long st = g * PIX + slot;
+    if (!cok || st >= nstrips) continue;
+    const Strip sp = strip_of(st, OH, SW);
+    float acc[kTW][VW];
+#pragma unroll
+    for (int b = 0; b < kTW; ++b)
+#pragma unroll
+      for (int e = 0; e < VW; ++e) acc[b][e] = 0.f;
+#pragma unroll 1
+    for (int i = 0; i < K; ++i) {
+      const int ih = sp.oh - P + i;
+      if (ih < 0 || ih >= IH) continue;
+      const T* wr = w + (long)((FLIP ? K - 1 - i : i) * K) * C + c0;
+      const T* xr = x + ((long)sp.n * IH + ih) * IW * ips + c0;
+      float ring[kTW][VW];  // ring[j % kTW] = w[i][j] for the taps j of the last kTW columns
+#pragma unroll
+      for (int jj = 0; jj < NC; ++jj) {
+        const int iw = sp.ow0 - P + jj;
+        const bool ok = iw >= 0 && iw < IW;
+        float xv[VW];
+        load_vec<T>(xr + (long)(ok ? iw : 0) * ips, xv);
+        if (jj < K) load_vec<T>(wr + (long)(FLIP ? K - 1 - jj : jj) * C, ring[jj % kTW]);
+#pragma unroll
+        for (int e = 0; e < VW; ++e) xv[e] = ok ? xv[e] : 0.f;
+#pragma unroll
+        for (int b = 0; b < kTW; ++b) {
+          const int j = jj - b;
+          if (j >= 0 && j < K) {
+#pragma unroll
+            for (int e = 0; e < VW; ++e) acc[b][e] += xv[e] * ring[j % kTW][e];
+          }
+        }
+      }
+    }
+#pragma unroll
+    for (int b = 0; b < kTW; ++b) {
+      const int ow = sp.ow0 + b;
+      if (ow >= OW) continue;
+      const long pix = ((long)sp.n * OH + sp.oh) * OW + ow;
+      T* yp = y + pix * ops + c0;
+      float f[VW];
+      if (EPI == EPI_ACC) {
+        if (accumulate) {
+          load_vec<T>(yp, f);
+#pragma unroll
+          for (int e = 0; e < VW; ++e) f[e] += acc[b][e];
+        } else {
+#pragma unroll
+          for (int e = 0; e < VW; ++e) f[e] = acc[b][e];
+        }
+      } else {
+#pragma unroll
+        for (int e = 0; e < VW; ++e) f[e] = to_f(from_f<T>(acc[b][e] + bs[e]));  // the value as stored
+        if (EPI == EPI_STATS) {
+#pragma unroll
+          for (int e = 0; e < VW; ++e) { s1[e] += f[e]; s2[e] += f[e] * f[e]; }
+        } else {
+          if (EPI == EPI_ACTBN) act_fwd_n<VW>(act, f);
+          if (scale) {
+#pragma unroll
+            for (int e = 0; e < VW; ++e) f[e] = f[e] * sc[e] + sh[e];
+          }
+          if (EPI == EPI_ACT) act_fwd_n<VW>(act, f);
+          if (res) {
+            float r[VW];
+            load_vec<T>(res + pix * rps + c0, r);
+#pragma unroll
+            for (int e = 0; e < VW; ++e) f[e] += r[e];
+          }
+        }
+      }
+      *reinterpret_cast<uint4*>(yp) = pack<T>(f);
+    }
+  }
+  if (EPI == EPI_STATS && psum) write_stat_rows<VW>(s1, s2, tcl, C, psum, psq);  // block-uniform
+}
+
+// 9 x 9 weight-grad partials, one filter row per blockIdx.z and one 16-byte channel vector per thread: 9 * VW
+// accumulators.  The strip's kTW dz vectors stay in registers while the kTW + 8 input columns of the row stream past;
+// part[blockIdx.x][(i * 9 + j) * C + c] for i = blockIdx.z, rows 81 * C floats apart.  Every block writes its whole row
+// slice (zeros without work), the rows are summed in row order by dw_wgrad_finalize_kernel.
+template <typename T>
+__global__ void __launch_bounds__(256)
+dw9_wgrad_kernel(const T* __restrict__ x, const T* __restrict__ dz, float* __restrict__ part, int N, int H, int W, int C,
+                 long xps, int OH, int OW, long zps, int tcl) {
+  constexpr int VW = Traits<T>::VW, K = 9, P = 4, NC = kTW - 1 + K;
+  const int TC = 1 << tcl, cu = threadIdx.x & (TC - 1), slot = threadIdx.x >> tcl, PIX = 256 >> tcl;
+  const int cv = blockIdx.y * TC + cu, i = blockIdx.z;
+  const bool cok = cv < C / VW;
+  const int c0 = cok ? cv * VW : 0;
+  const int SW = (OW + kTW - 1) / kTW;
+  const long nstrips = (long)N * OH * SW, ngroups = (nstrips + PIX - 1) / PIX;
+  float acc[K][VW];
+#pragma unroll
+  for (int j = 0; j < K; ++j)
+#pragma unroll
+    for (int e = 0; e < VW; ++e) acc[j][e] = 0.f;
+  for (long g = blockIdx.x; g < ngroups; g += gridDim.x) {
+    const long st = g * PIX + slot;
+    if (!cok || st >= nstrips) continue;
+    const Strip sp = strip_of(st, OH, SW);
+    const int ih = sp.oh - P + i;
+    if (ih < 0 || ih >= H) continue;
+    float zv[kTW][VW];
+    const T* zr = dz + ((long)sp.n * OH + sp.oh) * OW * zps + c0;
+#pragma unroll
+    for (int b = 0; b < kTW; ++b) {
+      const bool ok = sp.ow0 + b < OW;
+      load_vec<T>(zr + (long)(ok ? sp.ow0 + b : sp.ow0) * zps, zv[b]);
+#pragma unroll
+      for (int e = 0; e < VW; ++e) zv[b][e] = ok ? zv[b][e] : 0.f;
+    }
+    const T* xr = x + ((long)sp.n * H + ih) * W * xps + c0;
+#pragma unroll
+    for (int jj = 0; jj < NC; ++jj) {
+      const int iw = sp.ow0 - P + jj;
+      const bool ok = iw >= 0 && iw < W;
+      float xv[VW];
+      load_vec<T>(xr + (long)(ok ? iw : 0) * xps, xv);
+#pragma unroll
+      for (int e = 0; e < VW; ++e) xv[e] = ok ? xv[e] : 0.f;
+#pragma unroll
+      for (int b = 0; b < kTW; ++b) {
+        const int j = jj - b;
+        if (j >= 0 && j < K) {
+#pragma unroll
+          for (int e = 0; e < VW; ++e) acc[j][e] += xv[e] * zv[b][e];
+        }
+      }
+    }
+  }
+  __shared__ float red[4][32 * VW];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nch = TC * VW;
+  float* row = part + (long)blockIdx.x * K * K * C;
+#pragma unroll
+  for (int j = 0; j < K; ++j) {
+#pragma unroll
+    for (int e = 0; e < VW; ++e) {
+      const float a = unit_sum(acc[j][e], tcl);
+      if (lane < TC) red[wave][lane * VW + e] = a;
+    }
+    __syncthreads();
+    if ((int)threadIdx.x < nch) {
+      const int ch = blockIdx.y * nch + threadIdx.x;
+      if (ch < C) row[(long)(i * K + j) * C + ch] = ((red[0][threadIdx.x] + red[1][threadIdx.x]) + red[2][threadIdx.x]) + red[3][threadIdx.x];
+    }
+    __syncthreads();
+  }
+}
+
 // dw[c][tap] (torch OIHW of a (C, 1, K, K) weight) = (accumulate ? dw : 0) + the partial rows (RL floats apart) summed
 // in row order; db (nullable): the same for the bias gradient, whose share of a row follows its KK * C filter taps
 __global__ void __launch_bounds__(256)
@@ -445,7 +654,7 @@ bool geom_ok(int dtype, int N, int H, int W, int C, long xps, int KH, int KW, in
   const int VW = dtype ? 8 : 4;
   if (dtype != 0 && dtype != 1) return false;
   if (N < 1 || H < 1 || W < 1 || C < VW || C % VW) return false;
-  if (KH != KW || (KH != 3 && KH != 5 && KH != 7) || (S != 1 && S != 2) || (KH == 7 && S != 1) || P != KH / 2) return false;
+  if (KH != KW || (KH != 3 && KH != 5 && KH != 7 && KH != 9) || (S != 1 && S != 2) || (KH >= 7 && S != 1) || P != KH / 2) return false;
   if (OH != (H + 2 * P - KH) / S + 1 || OW != (W + 2 * P - KW) / S + 1 || OH < 1 || OW < 1) return false;
   if (xps < C || zps < C || xps % VW || zps % VW) return false;
   if ((long)N * H * W >= (1L << 31) || (long)N * OH * OW >= (1L << 31)) return false;
@@ -464,7 +673,7 @@ int rows_for(long M, int cap) {
   }
 #define DW_DISPATCH35(...)                                                                            \
   DW_K_S(3, 1, __VA_ARGS__) DW_K_S(3, 2, __VA_ARGS__) DW_K_S(5, 1, __VA_ARGS__) DW_K_S(5, 2, __VA_ARGS__)
-#define DW_DISPATCH(...) DW_DISPATCH35(__VA_ARGS__) DW_K_S(7, 1, __VA_ARGS__)  // k7 is stride 1 only (geom_ok)
+#define DW_DISPATCH(...) DW_DISPATCH35(__VA_ARGS__) DW_K_S(7, 1, __VA_ARGS__)  // k7 is stride 1 only (geom_ok); k9 has its own kernels
 
 template <typename T, int EPI>
 int launch_fwd(const void* x, const void* w, const float* bias, void* y, float* psum, float* psq, int N, int H, int W,
@@ -473,10 +682,18 @@ int launch_fwd(const void* x, const void* w, const float* bias, void* y, float* 
   const int tcl = tile_log2(C / Traits<T>::VW);
   const long M = (long)N * OH * OW;
   dim3 grid(rows_for(M, kFwdRowCap), ceil_div(C / Traits<T>::VW, 1 << tcl));
-  DW_DISPATCH((dw_conv_kernel<T, K_, S_, false, EPI><<<grid, 256, 0, st>>>(
-      (const T*)x, (const T*)w, bias, (T*)y, psum, psq, N, H, W, C, xps, OH, OW, yps, tcl, scale, shift, act,
-      (const T*)res, rps, 0)))
-  return (int)hipGetLastError();
+  if (KH == 9) {
+    dw9_conv_kernel<T, false, EPI><<<grid, 256, 0, st>>>((const T*)x, (const T*)w, bias, (T*)y, psum, psq, N, H, W, C, xps,
+                                                         OH, OW, yps, tcl, scale, shift, act, (const T*)res, rps, 0);
+    return (int)hipGetLastError();
+  }
+  if constexpr (EPI != EPI_ACTBN) {  // the act-then-BN epilogue exists for the 9 x 9 only
+    DW_DISPATCH((dw_conv_kernel<T, K_, S_, false, EPI><<<grid, 256, 0, st>>>(
+        (const T*)x, (const T*)w, bias, (T*)y, psum, psq, N, H, W, C, xps, OH, OW, yps, tcl, scale, shift, act,
+        (const T*)res, rps, 0)))
+    return (int)hipGetLastError();
+  }
+  return -1;
 }
 
 template <typename T>
@@ -484,6 +701,12 @@ int launch_dgrad(const void* dz, const void* w, void* dx, int accumulate, int N,
                  int S, int OH, int OW, long zps, hipStream_t st) {
   const int tcl = tile_log2(C / Traits<T>::VW);
   dim3 grid(rows_for((long)N * H * W, kFwdRowCap), ceil_div(C / Traits<T>::VW, 1 << tcl));
+  if (KH == 9) {
+    dw9_conv_kernel<T, true, EPI_ACC><<<grid, 256, 0, st>>>((const T*)dz, (const T*)w, nullptr, (T*)dx, nullptr, nullptr, N,
+                                                            OH, OW, C, zps, H, W, xps, tcl, nullptr, nullptr, 0, nullptr, 0,
+                                                            accumulate);
+    return (int)hipGetLastError();
+  }
   if (S == 1) {
     // correlation of dz (OH x OW) with the flipped filter, same padding (P = K / 2, K odd), output H x W
     DW_DISPATCH(if (S_ == 1) (dw_conv_kernel<T, K_, 1, true, EPI_ACC><<<grid, 256, 0, st>>>(
@@ -500,6 +723,13 @@ int launch_dgrad(const void* dz, const void* w, void* dx, int accumulate, int N,
 template <typename T>
 int launch_wgrad(const void* x, const void* dz, float* part, long RL, int bias, int N, int H, int W, int C, long xps,
                  int KH, int S, int OH, int OW, long zps, hipStream_t st) {
+  if (KH == 9) {  // a 16-byte channel vector per thread, one filter row per blockIdx.z
+    if (bias) return -1;
+    const int t9 = tile_log2(C / Traits<T>::VW);
+    dim3 g9(rows_for((long)N * OH * OW, kWgRowCap), ceil_div(C / Traits<T>::VW, 1 << t9), 9);
+    dw9_wgrad_kernel<T><<<g9, 256, 0, st>>>((const T*)x, (const T*)dz, part, N, H, W, C, xps, OH, OW, zps, t9);
+    return (int)hipGetLastError();
+  }
   const int tcl = tile_log2(C / kWgC);
   dim3 grid(rows_for((long)N * OH * OW, kWgRowCap), ceil_div(C / kWgC, 1 << tcl), KH == 7 ? 7 : 1);
   if (KH == 7) {
@@ -551,6 +781,21 @@ DMY_API int dmy_dwconv_fwd_act(int dtype, const void* x, const void* w, const fl
                                            shift, act, res, rps, st)
                : launch_fwd<float, EPI_ACT>(x, w, bias, y, nullptr, nullptr, N, H, W, C, xps, KH, S, OH, OW, yps, scale,
                                             shift, act, res, rps, st);
+}
+
+DMY_API int dmy_dwconv_fwd_actbn(int dtype, const void* x, const void* w, const float* bias, void* y, int N, int H, int W,
+                                 int C, long xps, int KH, int KW, int S, int P, int OH, int OW, long yps,
+                                 const float* scale, const float* shift, int act, const void* res, long rps,
+                                 void* stream) {
+  const int VW = dtype ? 8 : 4;
+  if (KH != 9 || !dmy_dwconv_ok(dtype, x, w, y, N, H, W, C, C, C, xps, KH, KW, S, P, OH, OW, yps) ||
+      (scale == nullptr) != (shift == nullptr) || (res && (!aligned16(res) || rps < C || rps % VW)))
+    return -1;
+  hipStream_t st = (hipStream_t)stream;
+  return dtype ? launch_fwd<bf16, EPI_ACTBN>(x, w, bias, y, nullptr, nullptr, N, H, W, C, xps, KH, S, OH, OW, yps, scale,
+                                             shift, act, res, rps, st)
+               : launch_fwd<float, EPI_ACTBN>(x, w, bias, y, nullptr, nullptr, N, H, W, C, xps, KH, S, OH, OW, yps, scale,
+                                              shift, act, res, rps, st);
 }
 
 DMY_API int dmy_dwconv_dgrad(int dtype, const void* dz, const void* w, void* dx, int accumulate, int N, int H, int W,

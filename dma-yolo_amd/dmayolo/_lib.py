@@ -52,6 +52,12 @@ SIGNATURES = {
     'dmy_dwconv_wgrad_finalize': [P, I, I, I, I, P, I, P],
     'dmy_dwconv_wgrad_bias': [I, P, P, P, I, I, I, I, L, I, I, I, I, I, I, L, P],
     'dmy_dwconv_wgrad_bias_finalize': [P, I, I, I, I, P, I, P, I, P],
+    'dmy_dwconv_fwd_actbn': [I, P, P, P, P, I, I, I, I, L, I, I, I, I, I, I, L, P, P, I, P, L, P],
+    # convmix.hip
+    'dmy_actbn_stats': [I, P, L, I, L, I, P, P, P],
+    'dmy_actbn_fwd': [I, P, L, I, P, P, P, L, P, L, L, I, P],
+    'dmy_actbn_bwd_reduce': [I, P, L, P, L, P, P, I, L, I, P, P, P],
+    'dmy_actbn_bwd_apply': [I, P, L, P, L, P, P, I, P, P, P, P, L, L, I, P, P],
     # adapt.hip
     'dmy_adapt_gate_blocks': [I, L, I, I],
     'dmy_adapt_gate_fwd': [I, I, P, L, I, P, L, I, P, L, I, P, L, P, P, P, L, P, L, P],

@@ -21,7 +21,7 @@ __all__ = ['autopad', 'Conv', 'DWConv', 'GhostConv', 'GhostBottleneck', 'C3Ghost
            'CABottleneck', 'C3CA', 'Concat', 'AdConcat2', 'AdConcat3', 'AdaptConcat', 'Adapt_Add2', 'Adapt_Add3', 'AdaptADD',
            'Upsample', 'C3STR', 'SwinTransformerBlock',
            'SwinTransformerLayer', 'WindowAttention', 'Mlp', 'DropPath', 'space_to_depth', 'SM', 'MP', 'DMConv', 'DMMConv',
-           'DMMConv2', 'SPP', 'CBAM', 'LayerNorm', 'GnConv', 'HorBlock', 'C3HB',
+           'DMMConv2', 'SPP', 'CBAM', 'LayerNorm', 'GnConv', 'HorBlock', 'C3HB', 'ConvMix', 'CSPCM',
            'ChannelAttentionModule', 'SpatialAttentionModule', 'C3TR', 'TransformerBlock', 'TransformerLayer']
 
 
@@ -853,8 +853,8 @@ class HorBlock(nn.Module):
                                         [out] if out is not None else None)
 
 
-class _HorStack(nn.Sequential):
-    """C3HB.m: the HorBlocks in sequence, the last one writing into C3's concat buffer"""
+class _OutStack(nn.Sequential):
+    """C3HB.m / CSPCM.m: blocks whose forward takes out= in sequence, the last one writing into C3's concat buffer"""
     dmy_out = True
 
     def forward(self, x, out=None):
@@ -870,7 +870,61 @@ class C3HB(C3):
     def __init__(self, c1, c2, n=1, shortcut=True, g=1, e=0.5):
         super().__init__(c1, c2, n, shortcut, g, e)
         c_ = int(c2 * e)
-        self.m = _HorStack(*(HorBlock(c_) for _ in range(n)))
+        self.m = _OutStack(*(HorBlock(c_) for _ in range(n)))
+
+
+# ------------------------------------------------------------------ ConvMixer: ConvMix / CSPCM (csrc/convmix.hip)
+
+class _ActBNStage(nn.Sequential):
+    """conv (with bias) -> GELU -> BatchNorm2d, the stage both halves of ConvMix are made of (models/cspcm.py:28-37),
+    with the reference's child indices 0 / 1 / 2.  The activation comes BEFORE the BN, so the stage runs on
+    Fn.conv_act_bn.  Model.fuse() leaves it alone, as the reference does (it fuses Conv / DWConv only)."""
+
+    def forward(self, x, res=None, xsink=None, rsink=None, out=None):
+        conv, act, bn = self[0], self[1], self[2]
+        k, s = conv.kernel_size[0], conv.stride[0]
+        pad = k // 2 if conv.padding == 'same' else _pad_int(conv.padding)
+        a = act_code(act)
+        return Fn.conv_act_bn(x, conv.weight, conv.bias, bn, s, pad, a, res=res, spec=Fn.spec_for(conv, s, pad, a, bn),
+                              xsink=xsink, rsink=rsink, out=out)
+
+
+class ConvMix(nn.Module):
+    """ConvMixer block, models/cspcm.py:25-41: x + BN(GELU(dw9x9(x))), then BN(GELU(conv1x1(.))); both convs biased.
+    The residual add rides on the first stage's act-BN pass (inference: on the depthwise launch itself).  As in the
+    reference, dim1 is not used."""
+
+    dmy_out = True  # forward(x, out=view) writes its result into a concat_buffer slice (C3.forward)
+
+    def __init__(self, dim, dim1, kernel_size=9):
+        super().__init__()
+        if kernel_size != 9:
+            raise NotImplementedError(f'ConvMix: kernel_size={kernel_size} has no gfx950 kernel (only the depthwise 9x9 of '
+                                      'models/cspcm.py:26)')
+        if dim % 4:
+            raise NotImplementedError(f'ConvMix: dim={dim} is not a whole number of 16-byte vectors (multiples of 4 '
+                                      'channels for float32, 8 for bfloat16)')
+        self.Resnet = _ActBNStage(nn.Conv2d(dim, dim, kernel_size=kernel_size, groups=dim, padding='same'), nn.GELU(),
+                                  nn.BatchNorm2d(dim))
+        self.Conv_1x1 = _ActBNStage(nn.Conv2d(dim, dim, kernel_size=1), nn.GELU(), nn.BatchNorm2d(dim))
+
+    def forward(self, x, out=None):
+        vw = Fn.VW.get(x.dtype)
+        if vw is None or x.shape[1] % vw:
+            raise NotImplementedError(f'ConvMix: {x.shape[1]} channels are not a whole number of 16-byte vectors of '
+                                      f'{x.dtype} (multiples of {vw})')
+        sk = Fn.GradSink(2)  # x -> the depthwise conv and the residual
+        x = self.Resnet(x, res=x, xsink=sk, rsink=sk)
+        return self.Conv_1x1(x, out=out)
+
+
+class CSPCM(C3):
+    """models/cspcm.py:43-54: C3's cv1 | cv2 -> concat -> cv3 around n ConvMix(c_, c_)."""
+
+    def __init__(self, c1, c2, n=1, e=0.5):
+        super().__init__(c1, c2, n, True, 1, e)
+        c_ = int(c2 * e)
+        self.m = _OutStack(*(ConvMix(c_, c_) for _ in range(n)))
 
 
 # ------------------------------------------------------------------ C3TR (config 5: global MHSA over P5 tokens)

@@ -539,6 +539,11 @@ def parse_model(d, ch):
             args = [ch[f]]
         elif m in (C.Concat, C.AdConcat2, C.AdConcat3):
             c2 = sum(ch[x] for x in f)
+        elif m in (C.ConvMix, C.CSPCM):  # models/yolo.py:409-413: n is NOT inserted, so number > 1 repeats the module
+            c1, c2 = ch[f], args[0]
+            if c2 != no:
+                c2 = make_divisible(c2 * gw, 8)
+            args = [c1, c2, *args[1:]]
         elif m in (C.AdaptConcat, C.AdaptADD):  # models/yolo.py:415-419
             c2 = sum(ch[x] for x in f)
             args = [len(f), *args]

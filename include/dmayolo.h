@@ -142,7 +142,7 @@ int dmy_conv_wgrad_to_oihw(const float* dw_ohwi, float* dw_oihw, int K, int C, i
  *      dmy_conv_wprep / dmy_conv_wprep_multi write for a (C, 1, k, k) OIHW weight (K = C, C = 1).
  *      Also nn.Conv2d(dim, dim, 7, padding=3, bias=True, groups=dim) of get_dwconv in GnConv (:1329, 1361-1362).
  *      dmy_dwconv_ok (models/common.py:79-82): 1 when the layer is supported -- groups == C == K, square k in
- *      {3, 5} with stride 1 or 2 or k = 7 with stride 1, padding k / 2, OH / OW the conv's output size, C a whole number of 16-byte vectors
+ *      {3, 5} with stride 1 or 2 or k in {7, 9} with stride 1, padding k / 2, OH / OW the conv's output size, C a whole number of 16-byte vectors
  *      (C % 8 bf16, C % 4 fp32), pixel strides >= C and whole vectors, 16-byte aligned bases.  Every other entry
  *      returns -1 and launches nothing when its arguments fail that test. */
 int dmy_dwconv_ok(int dtype, const void* x, const void* w, const void* z, int N, int H, int W, int C, int K, int groups,
@@ -178,6 +178,37 @@ int dmy_dwconv_wgrad_bias(int dtype, const void* x, const void* dz, float* part,
                           int KH, int KW, int S, int P, int OH, int OW, long zps, void* stream);
 int dmy_dwconv_wgrad_bias_finalize(const float* part, int rows, int C, int KH, int KW, float* dw, int accumulate,
                                    float* dbias, int bias_accumulate, void* stream);
+/* nn.Conv2d(dim, dim, 9, groups=dim, padding='same') of ConvMix.Resnet (models/cspcm.py:29): dmy_dwconv_ok also admits
+ * k = 9 with stride 1 and padding 4, and dmy_dwconv_fwd / _fwd_act / _dgrad / _wgrad / _wgrad_finalize take it (kernels
+ * of their own, the filter loaded per column; dmy_dwconv_wgrad_bias stays k = 7 only).
+ * dmy_dwconv_fwd_actbn is the one-launch inference form of x + BN(GELU(dw(x))) (models/cspcm.py:28-32, 39):
+ * y = act(T(conv + bias)) * scale + shift (+ res); scale / shift nullable together.  k = 9 only, -1 otherwise. */
+int dmy_dwconv_fwd_actbn(int dtype, const void* x, const void* w, const float* bias, void* y, int N, int H, int W, int C,
+                         long xps, int KH, int KW, int S, int P, int OH, int OW, long yps, const float* scale,
+                         const float* shift, int act, const void* res, long rps, void* stream);
+
+/* ---- activation before BatchNorm (csrc/convmix.hip): conv(+bias) -> GELU -> BatchNorm2d, both halves of ConvMix
+ *      (models/cspcm.py:28-37).  a = act(z) is recomputed from the stored pre-activation z [M][C] (pixel stride zps)
+ *      and never written.  16-byte vectors only: C a whole number of vectors, pixel strides >= C and whole vectors,
+ *      16-byte aligned bases; otherwise -1 and nothing is launched.  Every partial array is
+ *      [dmy_bn_partial_rows(M)][C], every row written, no atomics (run-to-run bit-identical).
+ * dmy_actbn_stats (models/cspcm.py:30-31, 35-36, train): per-block sums of a and a * a, for dmy_bn_finalize. */
+int dmy_actbn_stats(int dtype, const void* z, long zps, int act, long M, int C, float* psum, float* psq, void* stream);
+/* models/cspcm.py:30-31 / 35-36 and the residual of :39: y = act(z) * scale + shift (+ res); y may be a channel
+ * slice of a concat buffer (yps > C). */
+int dmy_actbn_fwd(int dtype, const void* z, long zps, int act, const float* scale, const float* shift, const void* res,
+                  long rps, void* y, long yps, long M, int C, void* stream);
+/* backward of models/cspcm.py:30-31 / 35-36, first pass: per-block sums of dy and dy * ahat, ahat = (a - mean) * invstd,
+ * for dmy_bn_bwd_finalize (-> dgamma, dbeta and the coefficients ca, cb, cc below). */
+int dmy_actbn_bwd_reduce(int dtype, const void* z, long zps, const void* dy, long dps, const float* mean,
+                         const float* invstd, int act, long M, int C, float* pdb, float* pdg, void* stream);
+/* backward of models/cspcm.py:30-31 / 35-36, second pass: dz = act'(z) * (ca * dy + cb + cc * ahat) -- train-mode BN
+ * with dmy_bn_bwd_finalize's coefficients, i.e. act'(z) * scale * (dy - mean(dy) - ahat * mean(dy * ahat)); eval mode:
+ * ca = scale, cb = cc = 0.  pdz (nullable): per-block sums of dz for dmy_reduce_rows, the gradient of the conv bias
+ * (models/cspcm.py:29, 34), which is not zero behind an activation. */
+int dmy_actbn_bwd_apply(int dtype, const void* z, long zps, const void* dy, long dps, const float* mean,
+                        const float* invstd, int act, const float* ca, const float* cb, const float* cc, void* dz,
+                        long dzps, long M, int C, float* pdz, void* stream);
 
 /* ---- adaptive-fusion necks (csrc/adapt.hip): AdaptConcat (models/common.py:953-992) and Adapt_Add2 / Adapt_Add3
  *      (models/common.py:1028-1061).  Streaming NHWC kernels, fp32 arithmetic, no atomics (run-to-run bit-identical).
