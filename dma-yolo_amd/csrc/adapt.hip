@@ -13,7 +13,7 @@
 // channels.  The backward accumulates the weight_levels / bias gradients in registers over the pixels a lane visits
 // and reduces them across the block in a fixed order into one partial row per block; dmy_reduce_rows sums the rows in
 // row order, so the result is bit-identical from run to run.
-#include "common.h"
+#include "launch.h"
 
 namespace {
 
@@ -301,8 +301,6 @@ adapt_add_bwd_kernel(Levels<T> A, const T* __restrict__ dy, long dps, const floa
         ((red[threadIdx.x][0] + red[threadIdx.x][1]) + red[threadIdx.x][2]) + red[threadIdx.x][3];
 }
 
-inline bool al16(const void* p) { return (((uintptr_t)p) & 15) == 0; }
-
 // lanes per pixel (log2): one per 16-byte vector of the concatenated row, at least one per level-map vector
 inline int gate_lpshift(int dtype, int Ct, int L) {
   const int VW = dtype ? 8 : 4, need = Ct / VW > 16 * L / VW ? Ct / VW : 16 * L / VW;
@@ -324,8 +322,8 @@ bool fill_levels(Levels<T>& A, int n, const void* const* x, const long* xps, con
     A.dxps[l] = on && dx ? dxps[l] : 0;
     A.voff[l] = off;
     if (!on) continue;
-    if (C[l] <= 0 || C[l] % VW || xps[l] % VW || xps[l] < C[l] || !x[l] || !al16(x[l])) return false;
-    if (dx && (!dx[l] || dxps[l] % VW || dxps[l] < C[l] || !al16(dx[l]))) return false;
+    if (C[l] <= 0 || !vec_ok(VW, C[l], {xps[l]}, {x[l]}) || xps[l] < C[l]) return false;
+    if (dx && (!vec_ok(VW, C[l], {dxps[l]}, {dx[l]}) || dxps[l] < C[l])) return false;
     off += C[l] / VW;
   }
   for (int l = n; l <= 3; ++l) A.voff[l] = off;
@@ -339,35 +337,24 @@ DMY_API int dmy_adapt_gate_blocks(int dtype, long M, int Ct, int L) {
   return grid_cap(ceil_div(M, gpb * 4), 2048);
 }
 
-#define GATE_DISPATCH(CALL)                              \
-  if (dtype) {                                           \
-    typedef bf16 T;                                      \
-    Levels<T> A;                                         \
-    if (!fill_levels<T>(A, L, xs, xps, Cs, dxs, dxps)) return -1; \
-    if (L == 2) { constexpr int L_ = 2; CALL; } else { constexpr int L_ = 3; CALL; } \
-  } else {                                               \
-    typedef float T;                                     \
-    Levels<T> A;                                         \
-    if (!fill_levels<T>(A, L, xs, xps, Cs, dxs, dxps)) return -1; \
-    if (L == 2) { constexpr int L_ = 2; CALL; } else { constexpr int L_ = 3; CALL; } \
-  }
-
 DMY_API int dmy_adapt_gate_fwd(int dtype, int L, const void* x0, long x0ps, int C0, const void* x1, long x1ps, int C1,
                                const void* x2, long x2ps, int C2, const void* wm, long wmps, const float* W,
                                const float* b, void* y, long yps, float* a, long M, void* stream) {
-  const int VW = dtype ? 8 : 4;
-  if (L < 2 || L > 3 || M < 1) return -1;
+  const int VW = vec_width(dtype), Ct = C0 + C1 + (L == 3 ? C2 : 0);
+  if (L < 2 || L > 3 || M < 1 || !vec_ok(VW, Ct, {wmps, yps}, {wm, y}) || wmps < 16 * L || yps < Ct || !W || !b || !a)
+    return -1;
   const void* xs[3] = {x0, x1, x2};
   const long xps[3] = {x0ps, x1ps, x2ps};
   const int Cs[3] = {C0, C1, C2};
-  void* const* dxs = nullptr;
-  const long* dxps = nullptr;
-  const int Ct = C0 + C1 + (L == 3 ? C2 : 0);
-  if (!wm || !al16(wm) || wmps % VW || wmps < 16 * L || !y || !al16(y) || yps % VW || yps < Ct || !W || !b || !a) return -1;
   const int sh = gate_lpshift(dtype, Ct, L), grid = dmy_adapt_gate_blocks(dtype, M, Ct, L);
-  hipStream_t st = (hipStream_t)stream;
-  GATE_DISPATCH((adapt_gate_fwd_kernel<T, L_><<<grid, 256, 0, st>>>(A, (const T*)wm, wmps, W, b, (T*)y, yps, a, M, sh)))
-  HIP_LAUNCH_CHECK();
+  return by_dtype(dtype, -1, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    Levels<T> A;
+    if (!fill_levels<T>(A, L, xs, xps, Cs, nullptr, nullptr)) return -1;
+    auto go = [&](auto nl) { return launch(adapt_gate_fwd_kernel<T, decltype(nl)::value>, grid, stream, A, wm, wmps, W,
+        b, y, yps, a, M, sh); };
+    return L == 2 ? go(Width<2>{}) : go(Width<3>{});
+  });
 }
 
 DMY_API int dmy_adapt_gate_bwd(int dtype, int L, const void* dy, long dps, const void* x0, long x0ps, int C0,
@@ -375,65 +362,61 @@ DMY_API int dmy_adapt_gate_bwd(int dtype, int L, const void* dy, long dps, const
                                const void* wm, long wmps, const float* W, void* dx0, long dx0ps, void* dx1, long dx1ps,
                                void* dx2, long dx2ps, int accumulate, void* dwm, long dwmps, float* pdw, float* pdb,
                                long M, void* stream) {
-  const int VW = dtype ? 8 : 4;
-  if (L < 2 || L > 3 || M < 1) return -1;
+  const int VW = vec_width(dtype), Ct = C0 + C1 + (L == 3 ? C2 : 0);
+  if (L < 2 || L > 3 || M < 1 || !vec_ok(VW, Ct, {wmps, dps, dwmps}, {wm, dy, dwm}) || wmps < 16 * L || dps < Ct ||
+      dwmps < 16 * L || !W || !a || !pdw || !pdb)
+    return -1;
   const void* xs[3] = {x0, x1, x2};
   const long xps[3] = {x0ps, x1ps, x2ps};
   const int Cs[3] = {C0, C1, C2};
   void* const dxs[3] = {dx0, dx1, dx2};
   const long dxps[3] = {dx0ps, dx1ps, dx2ps};
-  const int Ct = C0 + C1 + (L == 3 ? C2 : 0);
-  if (!wm || !al16(wm) || wmps % VW || wmps < 16 * L || !dy || !al16(dy) || dps % VW || dps < Ct || !dwm || !al16(dwm) ||
-      dwmps % VW || dwmps < 16 * L || !W || !a || !pdw || !pdb)
-    return -1;
   const int sh = gate_lpshift(dtype, Ct, L), grid = dmy_adapt_gate_blocks(dtype, M, Ct, L);
-  hipStream_t st = (hipStream_t)stream;
-  GATE_DISPATCH((adapt_gate_bwd_kernel<T, L_><<<grid, 256, 0, st>>>(A, (const T*)dy, dps, a, (const T*)wm, wmps, W,
-                                                                     accumulate, (T*)dwm, dwmps, pdw, pdb, M, sh)))
-  HIP_LAUNCH_CHECK();
+  return by_dtype(dtype, -1, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    Levels<T> A;
+    if (!fill_levels<T>(A, L, xs, xps, Cs, dxs, dxps)) return -1;
+    auto go = [&](auto nl) { return launch(adapt_gate_bwd_kernel<T, decltype(nl)::value>, grid, stream, A, dy, dps, a,
+        wm, wmps, W, accumulate, dwm, dwmps, pdw, pdb, M, sh); };
+    return L == 2 ? go(Width<2>{}) : go(Width<3>{});
+  });
 }
-
-#define ADD_DISPATCH(CALL)                               \
-  if (dtype) {                                           \
-    typedef bf16 T;                                      \
-    Levels<T> A;                                         \
-    if (!fill_levels<T>(A, n, xs, xps, Cs, dxs, dxps)) return -1; \
-    if (n == 2) { constexpr int N_ = 2; CALL; } else { constexpr int N_ = 3; CALL; } \
-  } else {                                               \
-    typedef float T;                                     \
-    Levels<T> A;                                         \
-    if (!fill_levels<T>(A, n, xs, xps, Cs, dxs, dxps)) return -1; \
-    if (n == 2) { constexpr int N_ = 2; CALL; } else { constexpr int N_ = 3; CALL; } \
-  }
 
 DMY_API int dmy_adapt_add_fwd(int dtype, int n, const void* x0, long x0ps, const void* x1, long x1ps, const void* x2,
                               long x2ps, const float* w, float eps, void* y, long yps, long M, int C, void* stream) {
-  const int VW = dtype ? 8 : 4;
-  if (n < 2 || n > 3 || M < 1 || !w || !y || !al16(y) || yps % VW || yps < C) return -1;
+  if (n < 2 || n > 3 || M < 1 || !w || !vec_ok(vec_width(dtype), C, {yps}, {y}) || yps < C) return -1;
   const void* xs[3] = {x0, x1, x2};
   const long xps[3] = {x0ps, x1ps, x2ps};
   const int Cs[3] = {C, C, C};
-  void* const* dxs = nullptr;
-  const long* dxps = nullptr;
   const int grid = dmy_dot_partial_blocks(M, C);
-  hipStream_t st = (hipStream_t)stream;
-  ADD_DISPATCH((adapt_add_fwd_kernel<T, N_><<<grid, 256, 0, st>>>(A, w, eps, (T*)y, yps, M, C)))
-  HIP_LAUNCH_CHECK();
+  return by_dtype(dtype, -1, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    Levels<T> A;
+    if (!fill_levels<T>(A, n, xs, xps, Cs, nullptr, nullptr)) return -1;
+    auto go = [&](auto ni) { return launch(adapt_add_fwd_kernel<T, decltype(ni)::value>, grid, stream, A, w, eps, y,
+        yps, M, C); };
+    return n == 2 ? go(Width<2>{}) : go(Width<3>{});
+  });
 }
 
 DMY_API int dmy_adapt_add_bwd(int dtype, int n, const void* dy, long dps, const void* x0, long x0ps, const void* x1,
                               long x1ps, const void* x2, long x2ps, const float* w, float eps, void* dx0, long dx0ps,
                               void* dx1, long dx1ps, void* dx2, long dx2ps, int accumulate, float* part, long M, int C,
                               void* stream) {
-  const int VW = dtype ? 8 : 4;
-  if (n < 2 || n > 3 || M < 1 || !w || !part || !dy || !al16(dy) || dps % VW || dps < C) return -1;
+  if (n < 2 || n > 3 || M < 1 || !w || !part || !vec_ok(vec_width(dtype), C, {dps}, {dy}) || dps < C) return -1;
   const void* xs[3] = {x0, x1, x2};
   const long xps[3] = {x0ps, x1ps, x2ps};
   const int Cs[3] = {C, C, C};
   void* const dxs[3] = {dx0, dx1, dx2};
   const long dxps[3] = {dx0ps, dx1ps, dx2ps};
   const int grid = dmy_dot_partial_blocks(M, C);
-  hipStream_t st = (hipStream_t)stream;
-  ADD_DISPATCH((adapt_add_bwd_kernel<T, N_><<<grid, 256, 0, st>>>(A, (const T*)dy, dps, w, eps, accumulate, part, M, C)))
-  HIP_LAUNCH_CHECK();
+  return by_dtype(dtype, -1, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    Levels<T> A;
+    if (!fill_levels<T>(A, n, xs, xps, Cs, dxs, dxps)) return -1;
+    auto go = [&](auto ni) { return launch(adapt_add_bwd_kernel<T, decltype(ni)::value>, grid, stream, A, dy, dps, w,
+        eps, accumulate, part, M, C); };
+    return n == 2 ? go(Width<2>{}) : go(Width<3>{});
+  });
 }
+

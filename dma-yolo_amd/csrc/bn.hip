@@ -5,7 +5,7 @@
 // sets 1e-3 / 0.03): normalise with the biased batch variance, update running_var with the
 // unbiased one.  Batch sums arrive as per-row-block partials (written by the conv epilogue or by
 // bn_stats below) and are finalised in f64.
-#include "common.h"
+#include "launch.h"
 
 namespace {
 
@@ -495,11 +495,6 @@ __global__ void colsum2_kernel(const float* __restrict__ a, const float* __restr
   }
 }
 
-inline bool vec_ok(int VW, int C, long s1, long s2, long s3, const void* p1, const void* p2, const void* p3) {
-  auto al = [](const void* p) { return p == nullptr || (((uintptr_t)p) & 15) == 0; };
-  return C % VW == 0 && s1 % VW == 0 && s2 % VW == 0 && s3 % VW == 0 && al(p1) && al(p2) && al(p3);
-}
-
 }  // namespace
 
 // grid of the vectorised streaming passes (blocks of 256 threads, RB rows per block and loop step), capped per kind
@@ -508,13 +503,7 @@ inline bool vec_ok(int VW, int C, long s1, long s2, long s3, const void* p1, con
 // write and sum), the elementwise ones (bn_act_fwd, bn_bwd_apply) at 16384 (apply 4.7 -> 5.2 TB/s, act 5.3 -> 5.5: more
 // rows in flight per CU); 4096 for the rest.  Round 6 fixed the caps and removed their switches, with the unroll
 // variants (DMY_BN_UNROLL 2 / 4, never faster than 1) and the row-order switch.
-inline int vec_grid_cap(long M, int C, int VW, int cap) {
-  const int RB = 256 / (C / VW);
-  return grid_cap(ceil_div(M, (long)RB * 8), cap);
-}
-inline int vec_grid(long M, int C, int VW) { return vec_grid_cap(M, C, VW, 4096); }
-inline int vec_grid_red(long M, int C, int VW) { return vec_grid_cap(M, C, VW, 2048); }
-inline int vec_grid_ew(long M, int C, int VW) { return vec_grid_cap(M, C, VW, 16384); }
+// These are launch.h's row_grid with kRedCap, kEwCap and 4096.
 // row order of the streaming passes: bn_act_fwd and bn_bwd_apply walk M from the END.  A pass that reads a tensor in
 // the reverse of the order its producer (or the previous pass) touched it starts on the lines still resident in the
 // 256 MiB Infinity Cache instead of the ones evicted first: conv writes z -> act reads z backwards (tail hot) and writes
@@ -531,20 +520,20 @@ DMY_API int dmy_bn_partial_rows(long M) {
 }
 
 DMY_API int dmy_bn_stats(int dtype, const void* z, long zps, long M, int C, float* psum, float* psq, void* stream) {
-  const int VW = dtype ? 8 : 4;
-  if (vec_ok(VW, C, zps, 0, 0, z, nullptr, nullptr) && C / VW <= 256) {
-    const int g = vec_grid_red(M, C, VW);
+  return by_dtype(dtype, kInvalid, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    constexpr int VW = Traits<T>::VW;
     hipStream_t st = (hipStream_t)stream;
-    if (dtype) bn_bwd_reduce_vec<bf16, true><<<g, 256, 0, st>>>((const bf16*)z, zps, (const bf16*)z, zps, nullptr, nullptr, nullptr, nullptr, 0, M, C, psum, psq, 0);
-    else bn_bwd_reduce_vec<float, true><<<g, 256, 0, st>>>((const float*)z, zps, (const float*)z, zps, nullptr, nullptr, nullptr, nullptr, 0, M, C, psum, psq, 0);
+    if (vec_ok(VW, C, {zps}, {}, {z}) && C / VW <= 256) {
+      bn_bwd_reduce_vec<T, true><<<row_grid(M, C, VW, kRedCap), 256, 0, st>>>(
+          (const T*)z, zps, (const T*)z, zps, nullptr, nullptr, nullptr, nullptr, 0, M, C, psum, psq, 0);
+    } else {
+      const int P = dmy_bn_partial_rows(M);
+      const int rpb = (int)((M + P - 1) / P);
+      bn_stats_kernel<T><<<dim3(P, ceil_div(C, 64)), 256, 0, st>>>((const T*)z, zps, M, C, rpb, psum, psq);
+    }
     return (int)hipGetLastError();
-  }
-  const int P = dmy_bn_partial_rows(M);
-  const int rpb = (int)((M + P - 1) / P);
-  dim3 grid(P, ceil_div(C, 64));
-  if (dtype) bn_stats_kernel<bf16><<<grid, 256, 0, (hipStream_t)stream>>>((const bf16*)z, zps, M, C, rpb, psum, psq);
-  else bn_stats_kernel<float><<<grid, 256, 0, (hipStream_t)stream>>>((const float*)z, zps, M, C, rpb, psum, psq);
-  return (int)hipGetLastError();
+  });
 }
 
 DMY_API int dmy_bn_finalize(const float* psum, const float* psq, int P, int C, double count, const float* gamma,
@@ -564,19 +553,18 @@ DMY_API int dmy_bn_eval_coef(const float* gamma, const float* beta, const float*
 
 DMY_API int dmy_bn_act_fwd(int dtype, const void* z, long zps, const float* scale, const float* shift, int act,
                            const void* res, long rps, void* y, long yps, long M, int C, void* stream) {
-  hipStream_t st = (hipStream_t)stream;
-  const int VW = dtype ? 8 : 4;
-  const bool vec = vec_ok(VW, C, zps, yps, res ? rps : 0, z, y, res) && C / VW <= 256;
-  if (vec) {
-    const int g = vec_grid_ew(M, C, VW);
-    if (dtype) bn_act_fwd_vec<bf16><<<g, 256, 0, st>>>((const bf16*)z, zps, scale, shift, act, (const bf16*)res, rps, (bf16*)y, yps, M, C, kRevAct);
-    else bn_act_fwd_vec<float><<<g, 256, 0, st>>>((const float*)z, zps, scale, shift, act, (const float*)res, rps, (float*)y, yps, M, C, kRevAct);
-  } else {
-    const int g = grid_cap(ceil_div(M * C, 256), 8192);
-    if (dtype) bn_act_fwd_scalar<bf16><<<g, 256, 0, st>>>((const bf16*)z, zps, scale, shift, act, (const bf16*)res, rps, (bf16*)y, yps, M, C);
-    else bn_act_fwd_scalar<float><<<g, 256, 0, st>>>((const float*)z, zps, scale, shift, act, (const float*)res, rps, (float*)y, yps, M, C);
-  }
-  return (int)hipGetLastError();
+  return by_dtype(dtype, kInvalid, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    constexpr int VW = Traits<T>::VW;
+    hipStream_t st = (hipStream_t)stream;
+    if (vec_ok(VW, C, {zps, yps, res ? rps : 0}, {}, {z, y, res}) && C / VW <= 256)
+      bn_act_fwd_vec<T><<<row_grid(M, C, VW, kEwCap), 256, 0, st>>>((const T*)z, zps, scale, shift, act, (const T*)res, rps,
+                                                                    (T*)y, yps, M, C, kRevAct);
+    else
+      bn_act_fwd_scalar<T><<<grid_cap(ceil_div(M * C, 256), 8192), 256, 0, st>>>((const T*)z, zps, scale, shift, act,
+                                                                                 (const T*)res, rps, (T*)y, yps, M, C);
+    return (int)hipGetLastError();
+  });
 }
 
 DMY_API int dmy_bn_act_f8_blocks(void) { return 1024; }
@@ -584,9 +572,8 @@ DMY_API int dmy_bn_act_f8_blocks(void) { return 1024; }
 DMY_API int dmy_bn_act_fwd_f8(const void* z, long zps, const float* scale, const float* shift, int act, const void* res,
                               long rps, void* y, long yps, long M, int C, void* y8, const float* pmax, float* nmax,
                               float* used, float headroom, float* nsat, void* stream) {
-  if (C % 8 != 0 || C / 8 > 256 || !vec_ok(8, C, zps, yps, res ? rps : 0, z, y, res) || ((uintptr_t)y8 & 7) ||
-      !(headroom >= 1.f))
-    return (int)hipErrorInvalidValue;
+  if (C / 8 > 256 || !vec_ok(8, C, {zps, yps, res ? rps : 0}, {}, {z, y, res}) || ((uintptr_t)y8 & 7) || !(headroom >= 1.f))
+    return kInvalid;
   const int G = dmy_bn_act_f8_blocks();
   bn_act_fwd_f8_kernel<<<G, 256, 0, (hipStream_t)stream>>>((const bf16*)z, zps, scale, shift, act, (const bf16*)res, rps,
                                                           (bf16*)y, yps, M, C, (unsigned char*)y8, pmax, G, nmax, used,
@@ -596,30 +583,29 @@ DMY_API int dmy_bn_act_fwd_f8(const void* z, long zps, const float* scale, const
 
 // Partial rows written by dmy_bn_bwd_reduce / dmy_bn_stats for these exact arguments.
 DMY_API int dmy_bn_reduce_rows(int dtype, const void* z, long zps, const void* dy, long dps, long M, int C) {
-  const int VW = dtype ? 8 : 4;
-  if (vec_ok(VW, C, zps, dy ? dps : 0, 0, z, dy, nullptr) && C / VW <= 256) return vec_grid_red(M, C, VW);
+  const int VW = vec_width(dtype);
+  if (vec_ok(VW, C, {zps, dy ? dps : 0}, {}, {z, dy}) && C / VW <= 256) return row_grid(M, C, VW, kRedCap);
   return dmy_bn_partial_rows(M);
 }
 
 DMY_API int dmy_bn_bwd_reduce(int dtype, const void* z, long zps, const void* dy, long dps, const float* scale,
                               const float* shift, const float* mean, const float* invstd, int act, long M, int C,
                               float* pdb, float* pdg, void* stream) {
-  hipStream_t st = (hipStream_t)stream;
-  const int VW = dtype ? 8 : 4;
-  if (vec_ok(VW, C, zps, dps, 0, z, dy, nullptr) && C / VW <= 256) {
-    const int g = vec_grid_red(M, C, VW);
-    if (dtype) bn_bwd_reduce_vec<bf16, false><<<g, 256, 0, st>>>((const bf16*)z, zps, (const bf16*)dy, dps, scale, shift, mean, invstd, act, M, C, pdb, pdg, kRevReduce);
-    else bn_bwd_reduce_vec<float, false><<<g, 256, 0, st>>>((const float*)z, zps, (const float*)dy, dps, scale, shift, mean, invstd, act, M, C, pdb, pdg, kRevReduce);
+  return by_dtype(dtype, kInvalid, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    constexpr int VW = Traits<T>::VW;
+    hipStream_t st = (hipStream_t)stream;
+    if (vec_ok(VW, C, {zps, dps}, {}, {z, dy}) && C / VW <= 256) {
+      bn_bwd_reduce_vec<T, false><<<row_grid(M, C, VW, kRedCap), 256, 0, st>>>(
+          (const T*)z, zps, (const T*)dy, dps, scale, shift, mean, invstd, act, M, C, pdb, pdg, kRevReduce);
+    } else {
+      const int P = dmy_bn_partial_rows(M);
+      const int rpb = (int)((M + P - 1) / P);
+      bn_bwd_reduce_kernel<T><<<dim3(P, ceil_div(C, 64)), 256, 0, st>>>((const T*)z, zps, (const T*)dy, dps, scale, shift,
+                                                                        mean, invstd, act, M, C, rpb, pdb, pdg);
+    }
     return (int)hipGetLastError();
-  }
-  const int P = dmy_bn_partial_rows(M);
-  const int rpb = (int)((M + P - 1) / P);
-  dim3 grid(P, ceil_div(C, 64));
-  if (dtype)
-    bn_bwd_reduce_kernel<bf16><<<grid, 256, 0, st>>>((const bf16*)z, zps, (const bf16*)dy, dps, scale, shift, mean, invstd, act, M, C, rpb, pdb, pdg);
-  else
-    bn_bwd_reduce_kernel<float><<<grid, 256, 0, st>>>((const float*)z, zps, (const float*)dy, dps, scale, shift, mean, invstd, act, M, C, rpb, pdb, pdg);
-  return (int)hipGetLastError();
+  });
 }
 
 DMY_API int dmy_colsum2_rows(long P) { return (int)(P < 256 ? P : 256); }
@@ -643,18 +629,18 @@ DMY_API int dmy_bn_bwd_finalize(const float* pdb, const float* pdg, int P, int C
 DMY_API int dmy_bn_bwd_apply(int dtype, const void* z, long zps, const void* dy, long dps, const float* scale,
                              const float* shift, const float* mean, const float* invstd, int act, const float* ca,
                              const float* cb, const float* cc, void* dz, long dzps, long M, int C, void* stream) {
-  hipStream_t st = (hipStream_t)stream;
-  const int VW = dtype ? 8 : 4;
-  if (vec_ok(VW, C, zps, dps, dzps, z, dy, dz) && C / VW <= 256) {
-    const int g = vec_grid_ew(M, C, VW);
-    if (dtype) bn_bwd_apply_vec<bf16><<<g, 256, 0, st>>>((const bf16*)z, zps, (const bf16*)dy, dps, scale, shift, mean, invstd, act, ca, cb, cc, (bf16*)dz, dzps, M, C, kRevApply);
-    else bn_bwd_apply_vec<float><<<g, 256, 0, st>>>((const float*)z, zps, (const float*)dy, dps, scale, shift, mean, invstd, act, ca, cb, cc, (float*)dz, dzps, M, C, kRevApply);
-  } else {
-    const int g = grid_cap(ceil_div(M * C, 256), 8192);
-    if (dtype) bn_bwd_apply_scalar<bf16><<<g, 256, 0, st>>>((const bf16*)z, zps, (const bf16*)dy, dps, scale, shift, mean, invstd, act, ca, cb, cc, (bf16*)dz, dzps, M, C);
-    else bn_bwd_apply_scalar<float><<<g, 256, 0, st>>>((const float*)z, zps, (const float*)dy, dps, scale, shift, mean, invstd, act, ca, cb, cc, (float*)dz, dzps, M, C);
-  }
-  return (int)hipGetLastError();
+  return by_dtype(dtype, kInvalid, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    constexpr int VW = Traits<T>::VW;
+    hipStream_t st = (hipStream_t)stream;
+    if (vec_ok(VW, C, {zps, dps, dzps}, {}, {z, dy, dz}) && C / VW <= 256)
+      bn_bwd_apply_vec<T><<<row_grid(M, C, VW, kEwCap), 256, 0, st>>>((const T*)z, zps, (const T*)dy, dps, scale, shift, mean,
+                                                                      invstd, act, ca, cb, cc, (T*)dz, dzps, M, C, kRevApply);
+    else
+      bn_bwd_apply_scalar<T><<<grid_cap(ceil_div(M * C, 256), 8192), 256, 0, st>>>(
+          (const T*)z, zps, (const T*)dy, dps, scale, shift, mean, invstd, act, ca, cb, cc, (T*)dz, dzps, M, C);
+    return (int)hipGetLastError();
+  });
 }
 
 // out[c] (+)= sum_p part[p][c]   (bias gradients from bn_stats partials)
@@ -819,14 +805,14 @@ __global__ void __launch_bounds__(256) scgate_bn_bwd_kernel(
 }  // namespace
 
 static bool scgate_bn_ok(int C, long xps, const void* x, const void* z, const void* g, const void* o) {
-  return C % 8 == 0 && C / 8 <= 256 && xps % 8 == 0 && vec_ok(8, C, xps, 0, 0, x, z, g) && vec_ok(8, C, 0, 0, 0, o, nullptr, nullptr);
+  return C / 8 <= 256 && vec_ok(8, C, {xps}, {}, {x, z, g, o});
 }
 
-DMY_API int dmy_scgate_bn_rows(int N, int H, int W, int C) { return vec_grid((long)N * H * W, C, 8); }
+DMY_API int dmy_scgate_bn_rows(int N, int H, int W, int C) { return row_grid((long)N * H * W, C, 8, 4096); }
 
 DMY_API int dmy_scgate_bn_fwd(const void* x, long xps, const void* z, const float* scale, const float* shift,
                               const void* g, void* out, int N, int H, int W, int C, int GH, int GW, void* stream) {
-  if (!scgate_bn_ok(C, xps, x, z, g, out)) return (int)hipErrorInvalidValue;
+  if (!scgate_bn_ok(C, xps, x, z, g, out)) return kInvalid;
   const int grid = dmy_scgate_bn_rows(N, H, W, C);
   scgate_bn_fwd_kernel<<<grid, 256, 0, (hipStream_t)stream>>>((const bf16*)x, xps, (const bf16*)z, scale, shift,
                                                               (const bf16*)g, (bf16*)out, N, H, W, C, GH, GW);
@@ -837,7 +823,7 @@ DMY_API int dmy_scgate_bn_bwd(const void* x, long xps, const void* z, const floa
                               const float* mean, const float* invstd, const void* g, const void* dout, void* du3,
                               void* dpre, int N, int H, int W, int C, int GH, int GW, float* pdb, float* pdg,
                               void* stream) {
-  if (!scgate_bn_ok(C, xps, x, z, g, du3) || !vec_ok(8, C, 0, 0, 0, dout, dpre, nullptr)) return (int)hipErrorInvalidValue;
+  if (!scgate_bn_ok(C, xps, x, z, g, du3) || !vec_ok(8, C, {}, {}, {dout, dpre})) return kInvalid;
   const int grid = dmy_scgate_bn_rows(N, H, W, C);
   scgate_bn_bwd_kernel<<<grid, 256, 0, (hipStream_t)stream>>>((const bf16*)x, xps, (const bf16*)z, scale, shift, mean,
                                                               invstd, (const bf16*)g, (const bf16*)dout, (bf16*)du3,

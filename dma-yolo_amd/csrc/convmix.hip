@@ -11,72 +11,10 @@
 // (the four waves through LDS, summed in wave order) -> one row per block: no atomics, run-to-run bit-identical.  The
 // rows have the format of dmy_bn_stats ([dmy_bn_partial_rows(M)][C]), so dmy_bn_finalize, dmy_bn_bwd_finalize,
 // dmy_colsum2 and dmy_reduce_rows finish them unchanged.
-#include "common.h"
+#include "launch.h"
+#include "tile.h"
 
 namespace {
-
-constexpr int kEwCap = 16384;  // grid cap of the elementwise pass (as bn.hip's vec_grid_ew)
-
-int tile_log2(int units) {
-  if (units <= 32) {
-    int l = 0;
-    while ((1 << l) < units) ++l;
-    return l;
-  }
-  int best = 5;
-  long pad = (long)ceil_div(units, 32) * 32;
-  for (int l = 4; l >= 3; --l) {
-    const long p = (long)ceil_div(units, 1 << l) * (1 << l);
-    if (p < pad) { pad = p; best = l; }
-  }
-  return best;
-}
-
-template <typename T> DEV void load_vec(const T* p, float* f) { unpack<T>(*reinterpret_cast<const uint4*>(p), f); }
-
-// sum over the lanes of a wave that share a channel unit (lane % TC), TC = 1 << tcl <= 32
-DEV float unit_sum(float v, int tcl) {
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1)
-    if (o >= (1 << tcl)) v += __shfl_xor(v, o, 64);
-  return v;
-}
-
-// this block's row of two [rows][C] partial arrays from the per-thread sums a, b; pb nullable with pa (block-uniform)
-template <int VW>
-DEV void write_rows(const float* a, const float* b, int tcl, int C, float* __restrict__ pa, float* __restrict__ pb) {
-  __shared__ float red[4][2 * 32 * VW];
-  const int TC = 1 << tcl, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-  for (int e = 0; e < VW; ++e) {
-    const float s = unit_sum(a[e], tcl), q = unit_sum(b[e], tcl);
-    if (lane < TC) {
-      red[wave][lane * VW + e] = s;
-      red[wave][32 * VW + lane * VW + e] = q;
-    }
-  }
-  __syncthreads();
-  const int nch = TC * VW;
-  for (int idx = threadIdx.x; idx < 2 * nch; idx += 256) {
-    const int half = idx >= nch, cc = idx - half * nch, ch = blockIdx.y * nch + cc;
-    if (ch < C && (half ? pb : pa)) {
-      const int o = half * 32 * VW + cc;
-      (half ? pb : pa)[(long)blockIdx.x * C + ch] = ((red[0][o] + red[1][o]) + red[2][o]) + red[3][o];
-    }
-  }
-}
-
-struct Tile {
-  int c0, rr, PIX;
-  bool cok;
-  DEV Tile(int tcl, int C, int VW) {
-    const int TC = 1 << tcl, cv = blockIdx.y * TC + (threadIdx.x & (TC - 1));
-    cok = cv < C / VW;
-    c0 = cok ? cv * VW : 0;
-    rr = threadIdx.x >> tcl;
-    PIX = 256 >> tcl;
-  }
-};
 
 // psum / psq: per-block sums of a = act(z) and a * a
 template <typename T>
@@ -203,56 +141,56 @@ actbn_bwd_apply_kernel(const T* __restrict__ z, long zps, const T* __restrict__ 
   if (pdz) write_rows<VW>(s1, s2, tcl, C, pdz, nullptr);  // block-uniform
 }
 
-bool vec_ok(int dtype, long M, int C, const void* p1, long s1, const void* p2, long s2, const void* p3, long s3) {
-  if (dtype != 0 && dtype != 1) return false;
-  const int VW = dtype ? 8 : 4;
-  auto ok = [&](const void* p, long s) { return p == nullptr || ((((uintptr_t)p) & 15) == 0 && s >= C && s % VW == 0); };
-  return M >= 1 && C >= VW && C % VW == 0 && p1 != nullptr && ok(p1, s1) && ok(p2, s2) && ok(p3, s3);
-}
-
 }  // namespace
 
 DMY_API int dmy_actbn_stats(int dtype, const void* z, long zps, int act, long M, int C, float* psum, float* psq,
                             void* stream) {
-  if (!vec_ok(dtype, M, C, z, zps, nullptr, 0, nullptr, 0) || !psum || !psq) return -1;
-  const int VW = dtype ? 8 : 4, tcl = tile_log2(C / VW);
-  dim3 grid(dmy_bn_partial_rows(M), ceil_div(C / VW, 1 << tcl));
-  hipStream_t st = (hipStream_t)stream;
-  if (dtype) actbn_stats_kernel<bf16><<<grid, 256, 0, st>>>((const bf16*)z, zps, act, M, C, tcl, psum, psq);
-  else actbn_stats_kernel<float><<<grid, 256, 0, st>>>((const float*)z, zps, act, M, C, tcl, psum, psq);
-  return (int)hipGetLastError();
+  const int VW = vec_width(dtype), tcl = tile_log2(C / VW);
+  if (!vec_ok(VW, C, {zps}, {z}) || M < 1 || C < VW || !rows_fit(C, {zps}) || !psum || !psq) return -1;
+  const dim3 grid = tile_grid(dmy_bn_partial_rows(M), C / VW, tcl);
+  return by_dtype(dtype, -1, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    return launch(actbn_stats_kernel<T>, grid, stream, z, zps, act, M, C, tcl, psum, psq);
+  });
 }
 
 DMY_API int dmy_actbn_fwd(int dtype, const void* z, long zps, int act, const float* scale, const float* shift,
                           const void* res, long rps, void* y, long yps, long M, int C, void* stream) {
-  if (!vec_ok(dtype, M, C, z, zps, y, yps, res, rps) || !y || !scale || !shift) return -1;
-  const int VW = dtype ? 8 : 4, tcl = tile_log2(C / VW);
-  dim3 grid(grid_cap(ceil_div(M, (long)(256 >> tcl) * 4), kEwCap), ceil_div(C / VW, 1 << tcl));
-  hipStream_t st = (hipStream_t)stream;
-  if (dtype) actbn_fwd_kernel<bf16><<<grid, 256, 0, st>>>((const bf16*)z, zps, act, scale, shift, (const bf16*)res, rps, (bf16*)y, yps, M, C, tcl);
-  else actbn_fwd_kernel<float><<<grid, 256, 0, st>>>((const float*)z, zps, act, scale, shift, (const float*)res, rps, (float*)y, yps, M, C, tcl);
-  return (int)hipGetLastError();
+  const int VW = vec_width(dtype), tcl = tile_log2(C / VW);
+  if (!vec_ok(VW, C, {zps, yps, res ? rps : 0}, {z, y}, {res}) || M < 1 || C < VW || !rows_fit(C, {zps, yps, res ? rps : C}) ||
+      !scale || !shift)
+    return -1;
+  const dim3 grid = tile_grid(grid_cap(ceil_div(M, (long)(256 >> tcl) * 4), kEwCap), C / VW, tcl);
+  return by_dtype(dtype, -1, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    return launch(actbn_fwd_kernel<T>, grid, stream, z, zps, act, scale, shift, res, rps, y, yps, M, C, tcl);
+  });
 }
 
 DMY_API int dmy_actbn_bwd_reduce(int dtype, const void* z, long zps, const void* dy, long dps, const float* mean,
                                  const float* invstd, int act, long M, int C, float* pdb, float* pdg, void* stream) {
-  if (!vec_ok(dtype, M, C, z, zps, dy, dps, nullptr, 0) || !dy || !mean || !invstd || !pdb || !pdg) return -1;
-  const int VW = dtype ? 8 : 4, tcl = tile_log2(C / VW);
-  dim3 grid(dmy_bn_partial_rows(M), ceil_div(C / VW, 1 << tcl));
-  hipStream_t st = (hipStream_t)stream;
-  if (dtype) actbn_bwd_reduce_kernel<bf16><<<grid, 256, 0, st>>>((const bf16*)z, zps, (const bf16*)dy, dps, mean, invstd, act, M, C, tcl, pdb, pdg);
-  else actbn_bwd_reduce_kernel<float><<<grid, 256, 0, st>>>((const float*)z, zps, (const float*)dy, dps, mean, invstd, act, M, C, tcl, pdb, pdg);
-  return (int)hipGetLastError();
+  const int VW = vec_width(dtype), tcl = tile_log2(C / VW);
+  if (!vec_ok(VW, C, {zps, dps}, {z, dy}) || M < 1 || C < VW || !rows_fit(C, {zps, dps}) || !mean || !invstd || !pdb || !pdg)
+    return -1;
+  const dim3 grid = tile_grid(dmy_bn_partial_rows(M), C / VW, tcl);
+  return by_dtype(dtype, -1, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    return launch(actbn_bwd_reduce_kernel<T>, grid, stream, z, zps, dy, dps, mean, invstd, act, M, C, tcl, pdb, pdg);
+  });
 }
 
 DMY_API int dmy_actbn_bwd_apply(int dtype, const void* z, long zps, const void* dy, long dps, const float* mean,
                                 const float* invstd, int act, const float* ca, const float* cb, const float* cc, void* dz,
                                 long dzps, long M, int C, float* pdz, void* stream) {
-  if (!vec_ok(dtype, M, C, z, zps, dy, dps, dz, dzps) || !dy || !dz || !mean || !invstd || !ca || !cb || !cc) return -1;
-  const int VW = dtype ? 8 : 4, tcl = tile_log2(C / VW);
-  dim3 grid(dmy_bn_partial_rows(M), ceil_div(C / VW, 1 << tcl));
-  hipStream_t st = (hipStream_t)stream;
-  if (dtype) actbn_bwd_apply_kernel<bf16><<<grid, 256, 0, st>>>((const bf16*)z, zps, (const bf16*)dy, dps, mean, invstd, act, ca, cb, cc, (bf16*)dz, dzps, M, C, tcl, pdz);
-  else actbn_bwd_apply_kernel<float><<<grid, 256, 0, st>>>((const float*)z, zps, (const float*)dy, dps, mean, invstd, act, ca, cb, cc, (float*)dz, dzps, M, C, tcl, pdz);
-  return (int)hipGetLastError();
+  const int VW = vec_width(dtype), tcl = tile_log2(C / VW);
+  if (!vec_ok(VW, C, {zps, dps, dzps}, {z, dy, dz}) || M < 1 || C < VW || !rows_fit(C, {zps, dps, dzps}) || !mean || !invstd ||
+      !ca || !cb || !cc)
+    return -1;
+  const dim3 grid = tile_grid(dmy_bn_partial_rows(M), C / VW, tcl);
+  return by_dtype(dtype, -1, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    return launch(actbn_bwd_apply_kernel<T>, grid, stream, z, zps, dy, dps, mean, invstd, act, ca, cb, cc, dz, dzps, M,
+        C, tcl, pdz);
+  });
 }
+

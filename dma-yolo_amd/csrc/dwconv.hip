@@ -16,7 +16,8 @@
 // Reductions (BN partials, weight-grad partials) go lane -> wave (xor shuffles over the lanes that share a channel
 // unit) -> block (the four waves through LDS, summed in wave order) -> one row per block; no atomics anywhere, so the
 // results are run-to-run bit-identical.
-#include "common.h"
+#include "launch.h"
+#include "tile.h"
 
 namespace {
 
@@ -24,43 +25,6 @@ constexpr int kTW = 4;            // output pixels per thread along W
 constexpr int kFwdRowCap = 1024;  // BN partial rows (== gridDim.x of the forward)
 constexpr int kWgRowCap = 512;    // weight-grad partial rows (== gridDim.x of the weight-grad)
 constexpr int kWgC = 4;           // channels per thread in the weight-grad (K * K * 4 accumulators; K = 7: K * 4)
-
-// channel units per block tile: the next power of two for <= 32 units, else the one of 32 / 16 / 8 that pads least
-int tile_log2(int units) {
-  if (units <= 32) {
-    int l = 0;
-    while ((1 << l) < units) ++l;
-    return l;
-  }
-  int best = 5;
-  long pad = (long)ceil_div(units, 32) * 32;
-  for (int l = 4; l >= 3; --l) {
-    const long p = (long)ceil_div(units, 1 << l) * (1 << l);
-    if (p < pad) { pad = p; best = l; }
-  }
-  return best;
-}
-
-template <typename T> DEV void load_vec(const T* p, float* f) { unpack<T>(*reinterpret_cast<const uint4*>(p), f); }
-
-DEV void load4(const float* p, float* f) {
-  const float4 v = *reinterpret_cast<const float4*>(p);
-  f[0] = v.x; f[1] = v.y; f[2] = v.z; f[3] = v.w;
-}
-DEV void load4(const bf16* p, float* f) {
-  const uint2 v = *reinterpret_cast<const uint2*>(p);
-  const bf16* e = reinterpret_cast<const bf16*>(&v);
-#pragma unroll
-  for (int i = 0; i < 4; ++i) f[i] = to_f(e[i]);
-}
-
-// sum over the lanes of a wave that share a channel unit (lane % TC), TC = 1 << tcl <= 32
-DEV float unit_sum(float v, int tcl) {
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1)
-    if (o >= (1 << tcl)) v += __shfl_xor(v, o, 64);
-  return v;
-}
 
 struct Strip {
   int n, oh, ow0;
@@ -174,6 +138,7 @@ dw_conv_kernel(const T* __restrict__ x, const T* __restrict__ w, const float* __
       *reinterpret_cast<uint4*>(yp) = pack<T>(f);
     }
   }
+  // tile.h's write_rows, inline: through the helper the bf16 instantiations compile to one SGPR fewer (usage is pinned)
   if (EPI == EPI_STATS && psum) {  // block-uniform: every thread reaches the barrier
     __shared__ float red[4][2 * 32 * VW];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -430,34 +395,6 @@ dw_wgrad_row_kernel(const T* __restrict__ x, const T* __restrict__ dz, float* __
 // 9 x 9").  Bounds as above: rows out of range are skipped, columns clamped to column 0 and zeroed, stores predicated.
 //   EPI_STATS / EPI_ACT / EPI_ACC: as dw_conv_kernel
 //   EPI_ACTBN: y = act(T(acc + bias)) * scale + shift (+ res)     (scale / shift nullable together)
-// this block's row of the two [rows][C] partial arrays from the per-thread sums s1 / s2: lanes that share a channel unit
-// -> the four waves through LDS, summed in wave order.  Every thread of the block must call it.  The same
-// steps as the tail of dw_conv_kernel, which stays inline there: through this helper its bf16 instantiations compile to
-// one SGPR fewer, and their resource usage is pinned to what it was.
-template <int VW>
-DEV void write_stat_rows(const float* s1, const float* s2, int tcl, int C, float* __restrict__ psum,
-                         float* __restrict__ psq) {
-  __shared__ float red[4][2 * 32 * VW];
-  const int TC = 1 << tcl, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-  for (int e = 0; e < VW; ++e) {
-    const float a = unit_sum(s1[e], tcl), q = unit_sum(s2[e], tcl);
-    if (lane < TC) {
-      red[wave][lane * VW + e] = a;
-      red[wave][32 * VW + lane * VW + e] = q;
-    }
-  }
-  __syncthreads();
-  const int nch = TC * VW;
-  for (int idx = threadIdx.x; idx < 2 * nch; idx += 256) {
-    const int half = idx >= nch, cc = idx - half * nch, ch = blockIdx.y * nch + cc;
-    if (ch < C) {
-      const int o = half * 32 * VW + cc;
-      (half ? psq : psum)[(long)blockIdx.x * C + ch] = ((red[0][o] + red[1][o]) + red[2][o]) + red[3][o];
-    }
-  }
-}
-
 template <typename T, bool FLIP, int EPI>
 __global__ void __launch_bounds__(256)
 dw9_conv_kernel(const T* __restrict__ x, const T* __restrict__ w, const float* __restrict__ bias, T* __restrict__ y,
@@ -554,7 +491,7 @@ dw9_conv_kernel(const T* __restrict__ x, const T* __restrict__ w, const float* _
       *reinterpret_cast<uint4*>(yp) = pack<T>(f);
     }
   }
-  if (EPI == EPI_STATS && psum) write_stat_rows<VW>(s1, s2, tcl, C, psum, psq);  // block-uniform
+  if (EPI == EPI_STATS && psum) write_rows<VW>(s1, s2, tcl, C, psum, psq);  // block-uniform
 }
 
 // 9 x 9 weight-grad partials, one filter row per blockIdx.z and one 16-byte channel vector per thread: 9 * VW
@@ -648,22 +585,13 @@ dw_wgrad_finalize_kernel(const float* __restrict__ part, int rows, int C, int KK
   dw[o] = accumulate ? dw[o] + s : s;
 }
 
-bool aligned16(const void* p) { return (((uintptr_t)p) & 15) == 0; }
-
 bool geom_ok(int dtype, int N, int H, int W, int C, long xps, int KH, int KW, int S, int P, int OH, int OW, long zps) {
-  const int VW = dtype ? 8 : 4;
   if (dtype != 0 && dtype != 1) return false;
-  if (N < 1 || H < 1 || W < 1 || C < VW || C % VW) return false;
+  if (N < 1 || H < 1 || W < 1 || C < vec_width(dtype) || !rows_fit(C, {xps, zps})) return false;
   if (KH != KW || (KH != 3 && KH != 5 && KH != 7 && KH != 9) || (S != 1 && S != 2) || (KH >= 7 && S != 1) || P != KH / 2) return false;
   if (OH != (H + 2 * P - KH) / S + 1 || OW != (W + 2 * P - KW) / S + 1 || OH < 1 || OW < 1) return false;
-  if (xps < C || zps < C || xps % VW || zps % VW) return false;
   if ((long)N * H * W >= (1L << 31) || (long)N * OH * OW >= (1L << 31)) return false;
   return true;
-}
-
-int rows_for(long M, int cap) {
-  const long r = (M + 255) / 256;
-  return (int)(r < 1 ? 1 : (r > cap ? cap : r));
 }
 
 #define DW_K_S(KK, SS, ...)                      \
@@ -676,85 +604,103 @@ int rows_for(long M, int cap) {
 #define DW_DISPATCH(...) DW_DISPATCH35(__VA_ARGS__) DW_K_S(7, 1, __VA_ARGS__)  // k7 is stride 1 only (geom_ok); k9 has its own kernels
 
 template <typename T, int EPI>
-int launch_fwd(const void* x, const void* w, const float* bias, void* y, float* psum, float* psq, int N, int H, int W,
-               int C, long xps, int KH, int S, int OH, int OW, long yps, const float* scale, const float* shift, int act,
-               const void* res, long rps, hipStream_t st) {
-  const int tcl = tile_log2(C / Traits<T>::VW);
-  const long M = (long)N * OH * OW;
-  dim3 grid(rows_for(M, kFwdRowCap), ceil_div(C / Traits<T>::VW, 1 << tcl));
+int launch_fwd(const T* x, const T* w, const float* bias, T* y, float* psum, float* psq, int N, int H, int W, int C,
+               long xps, int KH, int S, int OH, int OW, long yps, const float* scale, const float* shift, int act,
+               const T* res, long rps, hipStream_t st) {
+  constexpr int VW = Traits<T>::VW;
+  const int tcl = tile_log2(C / VW);
+  const dim3 grid = tile_grid(part_rows((long)N * OH * OW, kFwdRowCap), C / VW, tcl);
   if (KH == 9) {
-    dw9_conv_kernel<T, false, EPI><<<grid, 256, 0, st>>>((const T*)x, (const T*)w, bias, (T*)y, psum, psq, N, H, W, C, xps,
-                                                         OH, OW, yps, tcl, scale, shift, act, (const T*)res, rps, 0);
-    return (int)hipGetLastError();
+    return launch(dw9_conv_kernel<T, false, EPI>, grid, st, x, w, bias, y, psum, psq, N, H, W, C, xps, OH, OW, yps, tcl,
+        scale, shift, act, res, rps, 0);
   }
   if constexpr (EPI != EPI_ACTBN) {  // the act-then-BN epilogue exists for the 9 x 9 only
-    DW_DISPATCH((dw_conv_kernel<T, K_, S_, false, EPI><<<grid, 256, 0, st>>>(
-        (const T*)x, (const T*)w, bias, (T*)y, psum, psq, N, H, W, C, xps, OH, OW, yps, tcl, scale, shift, act,
-        (const T*)res, rps, 0)))
+    DW_DISPATCH((dw_conv_kernel<T, K_, S_, false, EPI><<<grid, 256, 0, st>>>(x, w, bias, y, psum, psq, N, H, W, C, xps, OH,
+                                                                             OW, yps, tcl, scale, shift, act, res, rps, 0)))
     return (int)hipGetLastError();
   }
   return -1;
 }
 
 template <typename T>
-int launch_dgrad(const void* dz, const void* w, void* dx, int accumulate, int N, int H, int W, int C, long xps, int KH,
-                 int S, int OH, int OW, long zps, hipStream_t st) {
-  const int tcl = tile_log2(C / Traits<T>::VW);
-  dim3 grid(rows_for((long)N * H * W, kFwdRowCap), ceil_div(C / Traits<T>::VW, 1 << tcl));
+int launch_dgrad(const T* dz, const T* w, T* dx, int accumulate, int N, int H, int W, int C, long xps, int KH, int S,
+                 int OH, int OW, long zps, hipStream_t st) {
+  constexpr int VW = Traits<T>::VW;
+  const int tcl = tile_log2(C / VW);
+  const dim3 grid = tile_grid(part_rows((long)N * H * W, kFwdRowCap), C / VW, tcl);
   if (KH == 9) {
-    dw9_conv_kernel<T, true, EPI_ACC><<<grid, 256, 0, st>>>((const T*)dz, (const T*)w, nullptr, (T*)dx, nullptr, nullptr, N,
-                                                            OH, OW, C, zps, H, W, xps, tcl, nullptr, nullptr, 0, nullptr, 0,
-                                                            accumulate);
-    return (int)hipGetLastError();
+    return launch(dw9_conv_kernel<T, true, EPI_ACC>, grid, st, dz, w, nullptr, dx, nullptr, nullptr, N, OH, OW, C, zps,
+        H, W, xps, tcl, nullptr, nullptr, 0, nullptr, 0, accumulate);
   }
   if (S == 1) {
     // correlation of dz (OH x OW) with the flipped filter, same padding (P = K / 2, K odd), output H x W
     DW_DISPATCH(if (S_ == 1) (dw_conv_kernel<T, K_, 1, true, EPI_ACC><<<grid, 256, 0, st>>>(
-        (const T*)dz, (const T*)w, nullptr, (T*)dx, nullptr, nullptr, N, OH, OW, C, zps, H, W, xps, tcl, nullptr, nullptr,
-        0, nullptr, 0, accumulate)))
+        dz, w, nullptr, dx, nullptr, nullptr, N, OH, OW, C, zps, H, W, xps, tcl, nullptr, nullptr, 0, nullptr, 0, accumulate)))
   } else {
-    DW_DISPATCH35(if (S_ == 2) (dw_dgrad_s2_kernel<T, K_><<<grid, 256, 0, st>>>(
-        (const T*)dz, (const T*)w, (T*)dx, accumulate, N, H, W, C, xps, OH, OW, zps, tcl)))
+    DW_DISPATCH35(if (S_ == 2) (dw_dgrad_s2_kernel<T, K_><<<grid, 256, 0, st>>>(dz, w, dx, accumulate, N, H, W, C, xps, OH,
+                                                                                OW, zps, tcl)))
   }
   return (int)hipGetLastError();
 }
 
 // RL: floats between partial rows; bias: the rows also carry the bias gradient's share (the row-per-z kernel only)
 template <typename T>
-int launch_wgrad(const void* x, const void* dz, float* part, long RL, int bias, int N, int H, int W, int C, long xps,
-                 int KH, int S, int OH, int OW, long zps, hipStream_t st) {
+int launch_wgrad(const T* x, const T* dz, float* part, long RL, int bias, int N, int H, int W, int C, long xps, int KH,
+                 int S, int OH, int OW, long zps, hipStream_t st) {
+  const int rows = part_rows((long)N * OH * OW, kWgRowCap);
   if (KH == 9) {  // a 16-byte channel vector per thread, one filter row per blockIdx.z
     if (bias) return -1;
     const int t9 = tile_log2(C / Traits<T>::VW);
-    dim3 g9(rows_for((long)N * OH * OW, kWgRowCap), ceil_div(C / Traits<T>::VW, 1 << t9), 9);
-    dw9_wgrad_kernel<T><<<g9, 256, 0, st>>>((const T*)x, (const T*)dz, part, N, H, W, C, xps, OH, OW, zps, t9);
-    return (int)hipGetLastError();
+    return launch(dw9_wgrad_kernel<T>, tile_grid(rows, C / Traits<T>::VW, t9, 9), st, x, dz, part, N, H, W, C, xps, OH,
+        OW, zps, t9);
   }
   const int tcl = tile_log2(C / kWgC);
-  dim3 grid(rows_for((long)N * OH * OW, kWgRowCap), ceil_div(C / kWgC, 1 << tcl), KH == 7 ? 7 : 1);
+  const dim3 grid = tile_grid(rows, C / kWgC, tcl, KH == 7 ? 7 : 1);
   if (KH == 7) {
-    dw_wgrad_row_kernel<T, 7, 1><<<grid, 256, 0, st>>>((const T*)x, (const T*)dz, part, RL, bias, N, H, W, C, xps, OH, OW,
-                                                       zps, tcl);
-    return (int)hipGetLastError();
+    return launch(dw_wgrad_row_kernel<T, 7, 1>, grid, st, x, dz, part, RL, bias, N, H, W, C, xps, OH, OW, zps, tcl);
   }
   if (bias) return -1;
-  DW_DISPATCH35((dw_wgrad_kernel<T, K_, S_><<<grid, 256, 0, st>>>((const T*)x, (const T*)dz, part, N, H, W, C, xps, OH,
-                                                                     OW, zps, tcl)))
+  DW_DISPATCH35((dw_wgrad_kernel<T, K_, S_><<<grid, 256, 0, st>>>(x, dz, part, N, H, W, C, xps, OH, OW, zps, tcl)))
   return (int)hipGetLastError();
+}
+
+// the one-launch inference forwards: EPI_ACT, or EPI_ACTBN (9 x 9 only)
+template <int EPI>
+int fwd_epilogue(int dtype, const void* x, const void* w, const float* bias, void* y, int N, int H, int W, int C, long xps,
+                 int KH, int KW, int S, int P, int OH, int OW, long yps, const float* scale, const float* shift, int act,
+                 const void* res, long rps, void* stream) {
+  if ((EPI == EPI_ACTBN && KH != 9) || !dmy_dwconv_ok(dtype, x, w, y, N, H, W, C, C, C, xps, KH, KW, S, P, OH, OW, yps) ||
+      (scale == nullptr) != (shift == nullptr) || (res && (!vec_ok(vec_width(dtype), C, {rps}, {res}) || rps < C)))
+    return -1;
+  return by_dtype(dtype, -1, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    return launch_fwd<T, EPI>((const T*)x, (const T*)w, bias, (T*)y, nullptr, nullptr, N, H, W, C, xps, KH, S, OH, OW, yps,
+                              scale, shift, act, (const T*)res, rps, (hipStream_t)stream);
+  });
+}
+
+int wgrad(int dtype, const void* x, const void* dz, float* part, int bias, int N, int H, int W, int C, long xps, int KH,
+          int KW, int S, int P, int OH, int OW, long zps, void* stream) {
+  if ((bias && KH != 7) || !dmy_dwconv_ok(dtype, x, part, dz, N, H, W, C, C, C, xps, KH, KW, S, P, OH, OW, zps)) return -1;
+  return by_dtype(dtype, -1, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    return launch_wgrad<T>((const T*)x, (const T*)dz, part, ((long)KH * KW + bias) * C, bias, N, H, W, C, xps, KH, S, OH, OW,
+                           zps, (hipStream_t)stream);
+  });
 }
 
 }  // namespace
 
+// the bases are checked for alignment only: a null base passes this query
 DMY_API int dmy_dwconv_ok(int dtype, const void* x, const void* w, const void* z, int N, int H, int W, int C, int K,
                           int groups, long xps, int KH, int KW, int S, int P, int OH, int OW, long zps) {
-  if (groups != C || K != C) return 0;
-  if (!aligned16(x) || !aligned16(w) || !aligned16(z)) return 0;
+  if (groups != C || K != C || !vec_ok(vec_width(dtype), C, {xps, zps}, {}, {x, w, z})) return 0;
   return geom_ok(dtype, N, H, W, C, xps, KH, KW, S, P, OH, OW, zps) ? 1 : 0;
 }
 
 DMY_API int dmy_dwconv_fwd_rows(long M, int C) {
   (void)C;
-  return rows_for(M, kFwdRowCap);
+  return part_rows(M, kFwdRowCap);
 }
 
 DMY_API int dmy_dwconv_fwd(int dtype, const void* x, const void* w, const float* bias, void* z, float* psum, float* psq,
@@ -762,71 +708,51 @@ DMY_API int dmy_dwconv_fwd(int dtype, const void* x, const void* w, const float*
                            void* stream) {
   if (!dmy_dwconv_ok(dtype, x, w, z, N, H, W, C, C, C, xps, KH, KW, S, P, OH, OW, zps) || (psum == nullptr) != (psq == nullptr))
     return -1;
-  hipStream_t st = (hipStream_t)stream;
-  return dtype ? launch_fwd<bf16, EPI_STATS>(x, w, bias, z, psum, psq, N, H, W, C, xps, KH, S, OH, OW, zps, nullptr,
-                                             nullptr, 0, nullptr, 0, st)
-               : launch_fwd<float, EPI_STATS>(x, w, bias, z, psum, psq, N, H, W, C, xps, KH, S, OH, OW, zps, nullptr,
-                                              nullptr, 0, nullptr, 0, st);
+  return by_dtype(dtype, -1, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    return launch_fwd<T, EPI_STATS>((const T*)x, (const T*)w, bias, (T*)z, psum, psq, N, H, W, C, xps, KH, S, OH, OW, zps,
+                                    nullptr, nullptr, 0, nullptr, 0, (hipStream_t)stream);
+  });
 }
 
 DMY_API int dmy_dwconv_fwd_act(int dtype, const void* x, const void* w, const float* bias, void* y, int N, int H, int W,
                                int C, long xps, int KH, int KW, int S, int P, int OH, int OW, long yps, const float* scale,
                                const float* shift, int act, const void* res, long rps, void* stream) {
-  const int VW = dtype ? 8 : 4;
-  if (!dmy_dwconv_ok(dtype, x, w, y, N, H, W, C, C, C, xps, KH, KW, S, P, OH, OW, yps) ||
-      (scale == nullptr) != (shift == nullptr) || (res && (!aligned16(res) || rps < C || rps % VW)))
-    return -1;
-  hipStream_t st = (hipStream_t)stream;
-  return dtype ? launch_fwd<bf16, EPI_ACT>(x, w, bias, y, nullptr, nullptr, N, H, W, C, xps, KH, S, OH, OW, yps, scale,
-                                           shift, act, res, rps, st)
-               : launch_fwd<float, EPI_ACT>(x, w, bias, y, nullptr, nullptr, N, H, W, C, xps, KH, S, OH, OW, yps, scale,
-                                            shift, act, res, rps, st);
+  return fwd_epilogue<EPI_ACT>(dtype, x, w, bias, y, N, H, W, C, xps, KH, KW, S, P, OH, OW, yps, scale, shift, act, res, rps,
+                               stream);
 }
 
 DMY_API int dmy_dwconv_fwd_actbn(int dtype, const void* x, const void* w, const float* bias, void* y, int N, int H, int W,
                                  int C, long xps, int KH, int KW, int S, int P, int OH, int OW, long yps,
                                  const float* scale, const float* shift, int act, const void* res, long rps,
                                  void* stream) {
-  const int VW = dtype ? 8 : 4;
-  if (KH != 9 || !dmy_dwconv_ok(dtype, x, w, y, N, H, W, C, C, C, xps, KH, KW, S, P, OH, OW, yps) ||
-      (scale == nullptr) != (shift == nullptr) || (res && (!aligned16(res) || rps < C || rps % VW)))
-    return -1;
-  hipStream_t st = (hipStream_t)stream;
-  return dtype ? launch_fwd<bf16, EPI_ACTBN>(x, w, bias, y, nullptr, nullptr, N, H, W, C, xps, KH, S, OH, OW, yps, scale,
-                                             shift, act, res, rps, st)
-               : launch_fwd<float, EPI_ACTBN>(x, w, bias, y, nullptr, nullptr, N, H, W, C, xps, KH, S, OH, OW, yps, scale,
-                                              shift, act, res, rps, st);
+  return fwd_epilogue<EPI_ACTBN>(dtype, x, w, bias, y, N, H, W, C, xps, KH, KW, S, P, OH, OW, yps, scale, shift, act, res,
+                                 rps, stream);
 }
 
 DMY_API int dmy_dwconv_dgrad(int dtype, const void* dz, const void* w, void* dx, int accumulate, int N, int H, int W,
                              int C, long xps, int KH, int KW, int S, int P, int OH, int OW, long zps, void* stream) {
   if (!dmy_dwconv_ok(dtype, dx, w, dz, N, H, W, C, C, C, xps, KH, KW, S, P, OH, OW, zps)) return -1;
-  hipStream_t st = (hipStream_t)stream;
-  return dtype ? launch_dgrad<bf16>(dz, w, dx, accumulate, N, H, W, C, xps, KH, S, OH, OW, zps, st)
-               : launch_dgrad<float>(dz, w, dx, accumulate, N, H, W, C, xps, KH, S, OH, OW, zps, st);
+  return by_dtype(dtype, -1, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    return launch_dgrad<T>((const T*)dz, (const T*)w, (T*)dx, accumulate, N, H, W, C, xps, KH, S, OH, OW, zps,
+                           (hipStream_t)stream);
+  });
 }
 
 DMY_API int dmy_dwconv_wgrad_rows(long M, int C) {
   (void)C;
-  return rows_for(M, kWgRowCap);
+  return part_rows(M, kWgRowCap);
 }
 
 DMY_API int dmy_dwconv_wgrad(int dtype, const void* x, const void* dz, float* part, int N, int H, int W, int C, long xps,
                              int KH, int KW, int S, int P, int OH, int OW, long zps, void* stream) {
-  if (!dmy_dwconv_ok(dtype, x, part, dz, N, H, W, C, C, C, xps, KH, KW, S, P, OH, OW, zps)) return -1;
-  hipStream_t st = (hipStream_t)stream;
-  const long RL = (long)KH * KW * C;
-  return dtype ? launch_wgrad<bf16>(x, dz, part, RL, 0, N, H, W, C, xps, KH, S, OH, OW, zps, st)
-               : launch_wgrad<float>(x, dz, part, RL, 0, N, H, W, C, xps, KH, S, OH, OW, zps, st);
+  return wgrad(dtype, x, dz, part, 0, N, H, W, C, xps, KH, KW, S, P, OH, OW, zps, stream);
 }
 
 DMY_API int dmy_dwconv_wgrad_bias(int dtype, const void* x, const void* dz, float* part, int N, int H, int W, int C,
                                   long xps, int KH, int KW, int S, int P, int OH, int OW, long zps, void* stream) {
-  if (KH != 7 || !dmy_dwconv_ok(dtype, x, part, dz, N, H, W, C, C, C, xps, KH, KW, S, P, OH, OW, zps)) return -1;
-  hipStream_t st = (hipStream_t)stream;
-  const long RL = ((long)KH * KW + 1) * C;
-  return dtype ? launch_wgrad<bf16>(x, dz, part, RL, 1, N, H, W, C, xps, KH, S, OH, OW, zps, st)
-               : launch_wgrad<float>(x, dz, part, RL, 1, N, H, W, C, xps, KH, S, OH, OW, zps, st);
+  return wgrad(dtype, x, dz, part, 1, N, H, W, C, xps, KH, KW, S, P, OH, OW, zps, stream);
 }
 
 DMY_API int dmy_dwconv_wgrad_finalize(const float* part, int rows, int C, int KH, int KW, float* dw, int accumulate,
@@ -846,3 +772,4 @@ DMY_API int dmy_dwconv_wgrad_bias_finalize(const float* part, int rows, int C, i
       part, rows, C, KK, (long)(KK + 1) * C, dw, accumulate, dbias, bias_accumulate);
   return (int)hipGetLastError();
 }
+

@@ -3,13 +3,10 @@
 //   nearest resize (nn.Upsample yaml:31/36, F.interpolate in SCConv :1311), channel-slice copy with
 //   BiFPN weights (Concat :656-664, AdConcat2/3 :994-1026), SCConv gate (:1311-1314),
 //   CoorAttention pooling / re-weighting (:1183-1207), input normalisation (train.py:402).
-#include "common.h"
-#include <initializer_list>
+#include "launch.h"
 #include <type_traits>
 
 namespace {
-
-inline bool al16(const void* p) { return p == nullptr || (((uintptr_t)p) & 15) == 0; }
 
 // NV = elements per thread: the 16-byte vector width (channels % VW == 0, 16-B aligned bases and
 // pixel strides) or 1 (scalar fallback).  All math per element in fp32, identical in both forms.
@@ -1149,35 +1146,6 @@ __global__ void cast_kernel(const S* __restrict__ x, D* __restrict__ y, long n, 
     y[i] = from_f<D>(to_f(x[i]) * scale);
 }
 
-// grid of the grid-stride elementwise kernels: blocks of 256 threads, capped at 16384 (DMA-1536 step 157.61 / 157.98
-// -> 158.13 / 158.32 img/s against 8192, alternating on one box, profiles/r05/elt_grid_ab.log)
-inline int egrid(long n) { return grid_cap(ceil_div(n, 256), 16384); }
-
-}  // namespace
-
-#define DISPATCH_T(dtype, ...)         \
-  if (dtype) {                         \
-    using T = bf16;                    \
-    __VA_ARGS__;                       \
-  } else {                             \
-    using T = float;                   \
-    __VA_ARGS__;                       \
-  }
-
-// T = storage type; NV = 16-byte vector width when `vec` holds, else 1 (scalar)
-#define DISPATCH_TV(dtype, vec, ...)                \
-  if (dtype) {                                      \
-    using T = bf16;                                 \
-    if (vec) { constexpr int NV = 8; __VA_ARGS__; } \
-    else { constexpr int NV = 1; __VA_ARGS__; }     \
-  } else {                                          \
-    using T = float;                                \
-    if (vec) { constexpr int NV = 4; __VA_ARGS__; } \
-    else { constexpr int NV = 1; __VA_ARGS__; }     \
-  }
-
-namespace {
-// all channel counts / pixel strides multiples of the 16-B vector and all bases 16-B aligned
 // Inference SPPF / SPPFCSPC pyramid (models/common.py:243-258, :1257-1276 under torch.no_grad): y1 = pool(x),
 // y2 = pool(y1), y3 = pool(y2) with the same k x k stride-1 window, in ONE launch instead of three.  The tile is loaded
 // with a 3P halo and the three pools run back to back in LDS, each over the region the next one needs, with
@@ -1279,132 +1247,154 @@ __global__ void __launch_bounds__(256) maxpool_chain3_lds(const T* __restrict__ 
   }
 }
 
-inline bool vec_ok(int dtype, std::initializer_list<long> ns, std::initializer_list<const void*> ps) {
-  const long VW = dtype ? 8 : 4;
-  for (long n : ns)
-    if (n % VW) return false;
-  for (const void* p : ps)
-    if (!al16(p)) return false;
-  return true;
-}
-inline long vw_of(int dtype, bool vec) { return vec ? (dtype ? 8 : 4) : 1; }
 }  // namespace
 
+// Below, `v` is the vector contract with every base nullable: where it fails, by_dtype_vec picks the scalar twin (NV = 1).
 DMY_API int dmy_maxpool_fwd(int dtype, const void* x, long xps, void* y, long yps, unsigned char* arg, int N, int H,
                             int W, int C, int k, void* stream) {
   hipStream_t st = (hipStream_t)stream;
-  const bool v = vec_ok(dtype, {C, xps, yps}, {x, y});
-  if (k < 1 || k > 15 || (k & 1) == 0) return (int)hipErrorInvalidValue;  // uint8 window offsets
-  if (v && N * (C / (dtype ? 8 : 4)) < 65536 && k >= 3 && k <= 13) {
-    const unsigned gl = (unsigned)ceil_div(W, MP_TW) * ceil_div(H, MP_TH) * N * (C / (dtype ? 8 : 4));  // mp_tile order
-#define MP_LDS(KS) if (dtype) maxpool_fwd_lds<bf16, KS><<<gl, 256, 0, st>>>((const bf16*)x, xps, (bf16*)y, yps, arg, H, W, C); \
-                   else maxpool_fwd_lds<float, KS><<<gl, 256, 0, st>>>((const float*)x, xps, (float*)y, yps, arg, H, W, C)
-    switch (k) {
-      case 3: MP_LDS(3); break;
-      case 5: MP_LDS(5); break;
-      case 7: MP_LDS(7); break;
-      case 9: MP_LDS(9); break;
-      case 11: MP_LDS(11); break;
-      default: MP_LDS(13); break;
-    }
+  const int VW = vec_width(dtype);
+  const bool v = vec_ok(VW, C, {xps, yps}, {}, {x, y});
+  if (k < 1 || k > 15 || (k & 1) == 0) return kInvalid;  // uint8 window offsets
+  if (v && N * (C / VW) < 65536 && k >= 3 && k <= 13) {
+    const unsigned gl = (unsigned)ceil_div(W, MP_TW) * ceil_div(H, MP_TH) * N * (C / VW);  // mp_tile order
+    return by_dtype(dtype, kInvalid, [&](auto tag) {
+      using T = typename decltype(tag)::type;
+#define MP_LDS(KS) maxpool_fwd_lds<T, KS><<<gl, 256, 0, st>>>((const T*)x, xps, (T*)y, yps, arg, H, W, C)
+      switch (k) {
+        case 3: MP_LDS(3); break;
+        case 5: MP_LDS(5); break;
+        case 7: MP_LDS(7); break;
+        case 9: MP_LDS(9); break;
+        case 11: MP_LDS(11); break;
+        default: MP_LDS(13); break;
+      }
 #undef MP_LDS
-    return (int)hipGetLastError();
+      return (int)hipGetLastError();
+    });
   }
-  const int g = egrid((long)N * H * W * C / (v ? (dtype ? 8 : 4) : 1));
-#define MP_FWD(KS) DISPATCH_TV(dtype, v, maxpool_fwd_kernel<T, NV, KS><<<g, 256, 0, st>>>((const T*)x, xps, (T*)y, yps, arg, N, H, W, C, k))
-  switch ((long)H * W * xps < (1L << 31) ? k : 0) {  // compile-time windows use 32-bit in-image offsets
-    case 3: MP_FWD(3); break;
-    case 5: MP_FWD(5); break;
-    case 7: MP_FWD(7); break;
-    case 9: MP_FWD(9); break;
-    case 11: MP_FWD(11); break;
-    case 13: MP_FWD(13); break;
-    default: MP_FWD(0); break;
-  }
+  const int g = vgrid((long)N * H * W * C / (v ? VW : 1));
+  return by_dtype_vec(dtype, v, kInvalid, [&](auto tag, auto nv) {
+    using T = typename decltype(tag)::type;
+    constexpr int NV = decltype(nv)::value;
+#define MP_FWD(KS) maxpool_fwd_kernel<T, NV, KS><<<g, 256, 0, st>>>((const T*)x, xps, (T*)y, yps, arg, N, H, W, C, k)
+    switch ((long)H * W * xps < (1L << 31) ? k : 0) {  // compile-time windows use 32-bit in-image offsets
+      case 3: MP_FWD(3); break;
+      case 5: MP_FWD(5); break;
+      case 7: MP_FWD(7); break;
+      case 9: MP_FWD(9); break;
+      case 11: MP_FWD(11); break;
+      case 13: MP_FWD(13); break;
+      default: MP_FWD(0); break;
+    }
 #undef MP_FWD
-  return (int)hipGetLastError();
+    return (int)hipGetLastError();
+  });
 }
 // y1 = pool(x), y2 = pool(y1), y3 = pool(y2) (k x k, stride 1, pad k / 2) in one launch, no argmax (inference); the
 // three outputs share the pixel stride yps (three channel slices of one concat buffer, or three tensors)
 DMY_API int dmy_maxpool_chain3_fwd(int dtype, const void* x, long xps, void* y1, void* y2, void* y3, long yps, int N,
                                    int H, int W, int C, int k, void* stream) {
   hipStream_t st = (hipStream_t)stream;
-  if (!vec_ok(dtype, {C, xps, yps}, {x, y1, y2, y3}) || (k != 3 && k != 5) || N * (C / (dtype ? 8 : 4)) >= 65536)
-    return (int)hipErrorInvalidValue;
+  const int VW = vec_width(dtype);
+  if (!vec_ok(VW, C, {xps, yps}, {}, {x, y1, y2, y3}) || (k != 3 && k != 5) || N * (C / VW) >= 65536) return kInvalid;
   // 16 x 32 tiles, or 8 x 16 when those leave most CUs idle (the 20^2 / 40^2 maps of batch-1 detect)
-  const long cv = N * (C / (dtype ? 8 : 4));
+  const long cv = N * (C / VW);
   const bool small = cv * ceil_div(W, 32) * ceil_div(H, 16) < 256;
   const unsigned gl = (unsigned)(cv * (small ? ceil_div(W, 16) * ceil_div(H, 8) : ceil_div(W, 32) * ceil_div(H, 16)));
-#define MP3(KS, TH, TW) if (dtype) maxpool_chain3_lds<bf16, KS, TH, TW><<<gl, 256, 0, st>>>((const bf16*)x, xps, (bf16*)y1, (bf16*)y2, (bf16*)y3, yps, H, W, C); \
-                        else maxpool_chain3_lds<float, KS, TH, TW><<<gl, 256, 0, st>>>((const float*)x, xps, (float*)y1, (float*)y2, (float*)y3, yps, H, W, C)
-  if (k == 5) {
-    if (small) MP3(5, 8, 16);
-    else MP3(5, 16, 32);
-  } else {
-    if (small) MP3(3, 8, 16);
-    else MP3(3, 16, 32);
-  }
+  return by_dtype(dtype, kInvalid, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+#define MP3(KS, TH, TW) maxpool_chain3_lds<T, KS, TH, TW><<<gl, 256, 0, st>>>((const T*)x, xps, (T*)y1, (T*)y2, (T*)y3, yps, H, W, C)
+    if (k == 5) {
+      if (small) MP3(5, 8, 16);
+      else MP3(5, 16, 32);
+    } else {
+      if (small) MP3(3, 8, 16);
+      else MP3(3, 16, 32);
+    }
 #undef MP3
-  return (int)hipGetLastError();
+    return (int)hipGetLastError();
+  });
 }
 DMY_API int dmy_maxpool_bwd(int dtype, const void* dy, long dps, const unsigned char* arg, void* dx, long dxps,
                             int accumulate, int N, int H, int W, int C, int k, void* stream) {
   hipStream_t st = (hipStream_t)stream;
-  const bool v = vec_ok(dtype, {C, dps, dxps}, {dy, dx});
-  if (k < 1 || k > 15 || (k & 1) == 0) return (int)hipErrorInvalidValue;
-  if (v && N * (C / (dtype ? 8 : 4)) < 65536 && k >= 3 && k <= 13) {
-    const unsigned gl = (unsigned)ceil_div(W, MP_TW) * ceil_div(H, MP_TH) * N * (C / (dtype ? 8 : 4));  // mp_tile order
-#define MP_LDS(KS) if (dtype) maxpool_bwd_lds<bf16, KS><<<gl, 256, 0, st>>>((const bf16*)dy, dps, arg, (bf16*)dx, dxps, accumulate, H, W, C); \
-                   else maxpool_bwd_lds<float, KS><<<gl, 256, 0, st>>>((const float*)dy, dps, arg, (float*)dx, dxps, accumulate, H, W, C)
-    switch (k) {
-      case 3: MP_LDS(3); break;
-      case 5: MP_LDS(5); break;
-      case 7: MP_LDS(7); break;
-      case 9: MP_LDS(9); break;
-      case 11: MP_LDS(11); break;
-      default: MP_LDS(13); break;
-    }
+  const int VW = vec_width(dtype);
+  const bool v = vec_ok(VW, C, {dps, dxps}, {}, {dy, dx});
+  if (k < 1 || k > 15 || (k & 1) == 0) return kInvalid;
+  if (v && N * (C / VW) < 65536 && k >= 3 && k <= 13) {
+    const unsigned gl = (unsigned)ceil_div(W, MP_TW) * ceil_div(H, MP_TH) * N * (C / VW);  // mp_tile order
+    return by_dtype(dtype, kInvalid, [&](auto tag) {
+      using T = typename decltype(tag)::type;
+#define MP_LDS(KS) maxpool_bwd_lds<T, KS><<<gl, 256, 0, st>>>((const T*)dy, dps, arg, (T*)dx, dxps, accumulate, H, W, C)
+      switch (k) {
+        case 3: MP_LDS(3); break;
+        case 5: MP_LDS(5); break;
+        case 7: MP_LDS(7); break;
+        case 9: MP_LDS(9); break;
+        case 11: MP_LDS(11); break;
+        default: MP_LDS(13); break;
+      }
 #undef MP_LDS
-    return (int)hipGetLastError();
+      return (int)hipGetLastError();
+    });
   }
-  DISPATCH_TV(dtype, v, maxpool_bwd_kernel<T, NV><<<egrid((long)N * H * W * C / NV), 256, 0, st>>>((const T*)dy, dps, arg, (T*)dx, dxps, accumulate, N, H, W, C, k));
-  return (int)hipGetLastError();
+  return by_dtype_vec(dtype, v, kInvalid, [&](auto tag, auto nv) {
+    using T = typename decltype(tag)::type;
+    constexpr int NV = decltype(nv)::value;
+    return launch(maxpool_bwd_kernel<T, NV>, vgrid((long)N * H * W * C / NV), st, dy, dps, arg, dx, dxps, accumulate, N,
+        H, W, C, k);
+  });
 }
 DMY_API int dmy_avgpool_fwd(int dtype, const void* x, long xps, void* y, int N, int H, int W, int C, int r,
                             void* stream) {
-  hipStream_t st = (hipStream_t)stream;
-  const bool v = vec_ok(dtype, {C, xps}, {x, y});
-  DISPATCH_TV(dtype, v, avgpool_fwd_kernel<T, NV><<<egrid((long)N * (H / r) * (W / r) * C / NV), 256, 0, st>>>((const T*)x, xps, (T*)y, N, H, W, C, r));
-  return (int)hipGetLastError();
+  const bool v = vec_ok(vec_width(dtype), C, {xps}, {}, {x, y});
+  return by_dtype_vec(dtype, v, kInvalid, [&](auto tag, auto nv) {
+    using T = typename decltype(tag)::type;
+    constexpr int NV = decltype(nv)::value;
+    return launch(avgpool_fwd_kernel<T, NV>, vgrid((long)N * (H / r) * (W / r) * C / NV), stream, x, xps, y, N, H, W, C,
+        r);
+  });
 }
 DMY_API int dmy_avgpool_bwd(int dtype, const void* dy, void* dx, long dxps, int accumulate, int N, int H, int W, int C,
                             int r, void* stream) {
-  hipStream_t st = (hipStream_t)stream;
-  const bool v = vec_ok(dtype, {C, dxps}, {dy, dx});
-  DISPATCH_TV(dtype, v, avgpool_bwd_kernel<T, NV><<<egrid((long)N * H * W * C / NV), 256, 0, st>>>((const T*)dy, (T*)dx, dxps, accumulate, N, H, W, C, r));
-  return (int)hipGetLastError();
+  const bool v = vec_ok(vec_width(dtype), C, {dxps}, {}, {dy, dx});
+  return by_dtype_vec(dtype, v, kInvalid, [&](auto tag, auto nv) {
+    using T = typename decltype(tag)::type;
+    constexpr int NV = decltype(nv)::value;
+    return launch(avgpool_bwd_kernel<T, NV>, vgrid((long)N * H * W * C / NV), stream, dy, dx, dxps, accumulate, N, H, W,
+        C, r);
+  });
 }
 DMY_API int dmy_resize_fwd(int dtype, const void* x, long xps, void* y, long yps, float yscale, int N, int IH, int IW,
                            int OH, int OW, int C, void* stream) {
-  hipStream_t st = (hipStream_t)stream;
-  const bool v = vec_ok(dtype, {C, xps, yps}, {x, y});
-  DISPATCH_TV(dtype, v, resize_fwd_kernel<T, NV><<<egrid((long)N * OH * OW * C / NV), 256, 0, st>>>((const T*)x, xps, (T*)y, yps, yscale, N, IH, IW, OH, OW, C));
-  return (int)hipGetLastError();
+  const bool v = vec_ok(vec_width(dtype), C, {xps, yps}, {}, {x, y});
+  return by_dtype_vec(dtype, v, kInvalid, [&](auto tag, auto nv) {
+    using T = typename decltype(tag)::type;
+    constexpr int NV = decltype(nv)::value;
+    return launch(resize_fwd_kernel<T, NV>, vgrid((long)N * OH * OW * C / NV), stream, x, xps, y, yps, yscale, N, IH,
+        IW, OH, OW, C);
+  });
 }
 DMY_API int dmy_resize_bwd(int dtype, const void* dy, long dps, void* dx, long dxps, int N, int IH, int IW, int OH,
                            int OW, int C, void* stream) {
-  hipStream_t st = (hipStream_t)stream;
-  const bool v = vec_ok(dtype, {C, dps, dxps}, {dy, dx});
-  DISPATCH_TV(dtype, v, resize_bwd_kernel<T, NV><<<egrid((long)N * IH * IW * C / NV), 256, 0, st>>>((const T*)dy, dps, (T*)dx, dxps, N, IH, IW, OH, OW, C));
-  return (int)hipGetLastError();
+  const bool v = vec_ok(vec_width(dtype), C, {dps, dxps}, {}, {dy, dx});
+  return by_dtype_vec(dtype, v, kInvalid, [&](auto tag, auto nv) {
+    using T = typename decltype(tag)::type;
+    constexpr int NV = decltype(nv)::value;
+    return launch(resize_bwd_kernel<T, NV>, vgrid((long)N * IH * IW * C / NV), stream, dy, dps, dx, dxps, N, IH, IW, OH,
+        OW, C);
+  });
 }
 DMY_API int dmy_space_to_depth(int dtype, const void* x, long xps, void* y, long yps, int N, int H, int W, int C,
                                int backward, void* stream) {
-  hipStream_t st = (hipStream_t)stream;
-  if ((H | W) & 1) return (int)hipErrorInvalidValue;  // the reference's cat needs even sizes
-  const bool v = vec_ok(dtype, {C, xps, yps}, {x, y});
-  DISPATCH_TV(dtype, v, s2d_kernel<T, NV><<<egrid((long)N * H * W * C / NV), 256, 0, st>>>((const T*)x, xps, (T*)y, yps, N, H, W, C, backward));
-  return (int)hipGetLastError();
+  if ((H | W) & 1) return kInvalid;  // the reference's cat needs even sizes
+  const bool v = vec_ok(vec_width(dtype), C, {xps, yps}, {}, {x, y});
+  return by_dtype_vec(dtype, v, kInvalid, [&](auto tag, auto nv) {
+    using T = typename decltype(tag)::type;
+    constexpr int NV = decltype(nv)::value;
+    return launch(s2d_kernel<T, NV>, vgrid((long)N * H * W * C / NV), stream, x, xps, y, yps, N, H, W, C, backward);
+  });
 }
 namespace {
 // pixel chunks of the global pool: about 2048 workgroups over (chunks x N x channel groups), >= 64
@@ -1427,38 +1417,48 @@ struct GPoolPlan {
 }  // namespace
 
 DMY_API long dmy_gpool_ws_bytes(int dtype, int N, int HW, int C) {
-  const GPoolPlan pl(N, HW, C, dtype ? 8 : 4);  // the vector plan has at least as many chunks as the scalar one
+  const GPoolPlan pl(N, HW, C, vec_width(dtype));  // the vector plan has at least as many chunks as the scalar one
   const GPoolPlan ps(N, HW, C, 1);
   return 3L * (pl.S > ps.S ? pl.S : ps.S) * N * C * 4;
 }
 DMY_API int dmy_gpool_fwd(int dtype, const void* x, long xps, int N, int HW, int C, void* out, int* arg, float* ws,
                           void* stream) {
   hipStream_t st = (hipStream_t)stream;
-  const bool v = vec_ok(dtype, {C, xps}, {x});
-  const GPoolPlan pl(N, HW, C, (int)vw_of(dtype, v));
-  const dim3 grid(pl.S, N, pl.groups);
-  DISPATCH_TV(dtype, v, gpool_part_kernel<T, NV><<<grid, 256, 0, st>>>((const T*)x, xps, N, HW, C, pl.L, pl.chunk, ws));
-  DISPATCH_T(dtype, gpool_final_kernel<T><<<egrid((long)N * C), 256, 0, st>>>(ws, pl.S, N, HW, C, (T*)out, arg));
-  return (int)hipGetLastError();
+  const bool v = vec_ok(vec_width(dtype), C, {xps}, {}, {x});
+  const GPoolPlan pl(N, HW, C, v ? vec_width(dtype) : 1);
+  return by_dtype_vec(dtype, v, kInvalid, [&](auto tag, auto nv) {
+    using T = typename decltype(tag)::type;
+    constexpr int NV = decltype(nv)::value;
+    gpool_part_kernel<T, NV><<<dim3(pl.S, N, pl.groups), 256, 0, st>>>((const T*)x, xps, N, HW, C, pl.L, pl.chunk, ws);
+    gpool_final_kernel<T><<<vgrid((long)N * C), 256, 0, st>>>(ws, pl.S, N, HW, C, (T*)out, arg);
+    return (int)hipGetLastError();
+  });
 }
 DMY_API int dmy_gpool_bwd(int dtype, const void* dz, const int* arg, void* dx, long dxps, int accumulate, int N, int HW,
                           int C, void* stream) {
-  hipStream_t st = (hipStream_t)stream;
-  const bool v = vec_ok(dtype, {C, dxps}, {dx});
-  DISPATCH_TV(dtype, v, gpool_bwd_kernel<T, NV><<<egrid((long)N * HW * C / NV), 256, 0, st>>>((const T*)dz, arg, (T*)dx, dxps, accumulate, N, HW, C));
-  return (int)hipGetLastError();
+  const bool v = vec_ok(vec_width(dtype), C, {dxps}, {}, {dx});
+  return by_dtype_vec(dtype, v, kInvalid, [&](auto tag, auto nv) {
+    using T = typename decltype(tag)::type;
+    constexpr int NV = decltype(nv)::value;
+    return launch(gpool_bwd_kernel<T, NV>, vgrid((long)N * HW * C / NV), stream, dz, arg, dx, dxps, accumulate, N, HW,
+        C);
+  });
 }
 DMY_API int dmy_halves_sigmoid(int dtype, const void* z, int N, int C, void* ca, const void* dca, void* dz, void* stream) {
-  hipStream_t st = (hipStream_t)stream;
-  DISPATCH_T(dtype, halves_sigmoid_kernel<T><<<egrid((long)N * C), 256, 0, st>>>((const T*)z, N, C, (T*)ca, (const T*)dca, (T*)dz));
-  return (int)hipGetLastError();
+  return by_dtype(dtype, kInvalid, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    return launch(halves_sigmoid_kernel<T>, vgrid((long)N * C), stream, z, N, C, ca, dca, dz);
+  });
 }
 DMY_API int dmy_cbam_in_fwd(int dtype, const void* x, long xps, const void* ca, int N, int HW, int C, void* out1, void* s2,
                             int* am, void* stream) {
-  hipStream_t st = (hipStream_t)stream;
-  const bool v = vec_ok(dtype, {C, xps}, {x, ca, out1});
-  DISPATCH_TV(dtype, v, cbam_in_fwd_kernel<T, NV><<<grid_cap(ceil_div((long)N * HW, 4), 8192), 256, 0, st>>>((const T*)x, xps, (const T*)ca, N, HW, C, (T*)out1, (T*)s2, am));
-  return (int)hipGetLastError();
+  const bool v = vec_ok(vec_width(dtype), C, {xps}, {}, {x, ca, out1});
+  return by_dtype_vec(dtype, v, kInvalid, [&](auto tag, auto nv) {
+    using T = typename decltype(tag)::type;
+    constexpr int NV = decltype(nv)::value;
+    return launch(cbam_in_fwd_kernel<T, NV>, grid_cap(ceil_div((long)N * HW, 4), 8192), stream, x, xps, ca, N, HW, C,
+        out1, s2, am);
+  });
 }
 static const int kCbamPpw = 64;  // pixels per wave of cbam_in_bwd_kernel
 DMY_API long dmy_cbam_in_bwd_ws_elems(int N, int HW, int C) {
@@ -1468,53 +1468,66 @@ DMY_API int dmy_cbam_in_bwd(int dtype, const void* x, long xps, const void* ca, 
                             const void* ds2, const int* am, int N, int HW, int C, void* dx, long dxps, int accumulate,
                             float* dca, float* ws, void* stream) {
   hipStream_t st = (hipStream_t)stream;
-  const bool v = vec_ok(dtype, {C, xps, dps, dxps}, {x, ca, dout1, dx});
+  const bool v = vec_ok(vec_width(dtype), C, {xps, dps, dxps}, {}, {x, ca, dout1, dx});
   const int wpi = (int)ceil_div((long)HW, kCbamPpw);
   const long waves = (long)N * wpi;
-  DISPATCH_TV(dtype, v, cbam_in_bwd_kernel<T, NV><<<(unsigned)ceil_div(waves, 4), 256, 0, st>>>((const T*)x, xps, (const T*)ca, (const T*)dout1, dps, (const T*)ds2, am, N, HW, C, kCbamPpw, wpi, (T*)dx, dxps, accumulate, ws));
-  cbam_fold_kernel<<<grid_cap(ceil_div((long)N * C, 256)), 256, 0, st>>>(ws, N, C, wpi, dca);
-  return (int)hipGetLastError();
+  return by_dtype_vec(dtype, v, kInvalid, [&](auto tag, auto nv) {
+    using T = typename decltype(tag)::type;
+    constexpr int NV = decltype(nv)::value;
+    cbam_in_bwd_kernel<T, NV><<<(unsigned)ceil_div(waves, 4), 256, 0, st>>>(
+        (const T*)x, xps, (const T*)ca, (const T*)dout1, dps, (const T*)ds2, am, N, HW, C, kCbamPpw, wpi, (T*)dx, dxps,
+        accumulate, ws);
+    cbam_fold_kernel<<<grid_cap(ceil_div((long)N * C, 256)), 256, 0, st>>>(ws, N, C, wpi, dca);
+    return (int)hipGetLastError();
+  });
 }
 DMY_API int dmy_pixscale(int dtype, const void* out1, const void* sa, long sps, int N, int HW, int C, void* out, long ops,
                          const void* dout, long dps, void* dout1, void* dsa, void* stream) {
-  hipStream_t st = (hipStream_t)stream;
-  const bool v = vec_ok(dtype, {C, ops, dout ? dps : 0}, {out1, out, dout, dout1});
-  DISPATCH_TV(dtype, v, pixscale_kernel<T, NV><<<grid_cap(ceil_div((long)N * HW, 4), 8192), 256, 0, st>>>((const T*)out1, (const T*)sa, sps, N, HW, C, (T*)out, ops, (const T*)dout, dps, (T*)dout1, (T*)dsa));
-  return (int)hipGetLastError();
+  const bool v = vec_ok(vec_width(dtype), C, {ops, dout ? dps : 0}, {}, {out1, out, dout, dout1});
+  return by_dtype_vec(dtype, v, kInvalid, [&](auto tag, auto nv) {
+    using T = typename decltype(tag)::type;
+    constexpr int NV = decltype(nv)::value;
+    return launch(pixscale_kernel<T, NV>, grid_cap(ceil_div((long)N * HW, 4), 8192), stream, out1, sa, sps, N, HW, C,
+        out, ops, dout, dps, dout1, dsa);
+  });
 }
 DMY_API int dmy_slice_copy(int dtype, const void* src, long sps, void* dst, long dps, long M, int C, const float* wv,
                            int idx, int nw, float eps, int accumulate, void* stream) {
-  hipStream_t st = (hipStream_t)stream;
-  const int VW = dtype ? 8 : 4;
-  const bool vec = C % VW == 0 && sps % VW == 0 && dps % VW == 0 && al16(src) && al16(dst);
+  const int VW = vec_width(dtype);
+  const bool vec = vec_ok(VW, C, {sps, dps}, {}, {src, dst});
   const long work = M * (vec ? C / VW : C);
-  if (vec) {
-    DISPATCH_T(dtype, slice_copy_kernel<T, true><<<egrid(work), 256, 0, st>>>((const T*)src, sps, (T*)dst, dps, M, C, wv, idx, nw, eps, accumulate));
-  } else {
-    DISPATCH_T(dtype, slice_copy_kernel<T, false><<<egrid(work), 256, 0, st>>>((const T*)src, sps, (T*)dst, dps, M, C, wv, idx, nw, eps, accumulate));
-  }
-  return (int)hipGetLastError();
+  return by_dtype(dtype, kInvalid, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    auto launch = [&](auto vt) {
+      slice_copy_kernel<T, decltype(vt)::value><<<vgrid(work), 256, 0, (hipStream_t)stream>>>(
+          (const T*)src, sps, (T*)dst, dps, M, C, wv, idx, nw, eps, accumulate);
+    };
+    if (vec) launch(std::true_type{});
+    else launch(std::false_type{});
+    return (int)hipGetLastError();
+  });
 }
 DMY_API int dmy_dot_partial_blocks(long M, int C) { return grid_cap(ceil_div(M * C, 256 * 64), 2048); }
 DMY_API int dmy_dot_partial(int dtype, const void* a, long aps, const void* b, long bps, long M, int C, float* part,
                             void* stream) {
-  hipStream_t st = (hipStream_t)stream;
-  const int nb = dmy_dot_partial_blocks(M, C);
-  const bool v = vec_ok(dtype, {C, aps, bps}, {a, b});
-  DISPATCH_TV(dtype, v, dot_partial_kernel<T, NV><<<nb, 256, 0, st>>>((const T*)a, aps, (const T*)b, bps, M, C, part));
-  return (int)hipGetLastError();
+  const bool v = vec_ok(vec_width(dtype), C, {aps, bps}, {}, {a, b});
+  return by_dtype_vec(dtype, v, kInvalid, [&](auto tag, auto nv) {
+    using T = typename decltype(tag)::type;
+    constexpr int NV = decltype(nv)::value;
+    return launch(dot_partial_kernel<T, NV>, dmy_dot_partial_blocks(M, C), stream, a, aps, b, bps, M, C, part);
+  });
 }
 // dmy_slice_copy (accumulate as given) + dmy_dot_partial(dy, x) in one launch; part gets dmy_dot_partial_blocks(M, C)
 // partials.  16-B vectors only (returns hipErrorInvalidValue otherwise: use the two calls)
 DMY_API int dmy_slice_copy_dot(int dtype, const void* dy, long dps, void* g, long gps, const void* x, long xps, long M,
                                int C, const float* wv, int idx, int nw, float eps, int accumulate, float* part,
                                void* stream) {
-  if (!vec_ok(dtype, {C, dps, gps, xps}, {dy, g, x})) return (int)hipErrorInvalidValue;
-  const int nb = dmy_dot_partial_blocks(M, C);
-  hipStream_t st = (hipStream_t)stream;
-  DISPATCH_T(dtype, slice_copy_dot_kernel<T><<<nb, 256, 0, st>>>((const T*)dy, dps, (T*)g, gps, (const T*)x, xps, M, C,
-                                                                  wv, idx, nw, eps, accumulate, part));
-  return (int)hipGetLastError();
+  if (!vec_ok(vec_width(dtype), C, {dps, gps, xps}, {}, {dy, g, x})) return kInvalid;
+  return by_dtype(dtype, kInvalid, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    return launch(slice_copy_dot_kernel<T>, dmy_dot_partial_blocks(M, C), stream, dy, dps, g, gps, x, xps, M, C, wv,
+        idx, nw, eps, accumulate, part);
+  });
 }
 DMY_API int dmy_bifpn_wgrad(const float* part, int nblk, int nw, const float* wv, float eps, float* dw, void* stream) {
   bifpn_wgrad_kernel<<<1, 64, 0, (hipStream_t)stream>>>(part, nblk, nw, wv, eps, dw);
@@ -1522,43 +1535,57 @@ DMY_API int dmy_bifpn_wgrad(const float* part, int nblk, int nw, const float* wv
 }
 DMY_API int dmy_scgate_fwd(int dtype, const void* x, long xps, const void* u3, const void* g, void* out, int N, int H,
                            int W, int C, int GH, int GW, void* stream) {
-  hipStream_t st = (hipStream_t)stream;
-  const bool v = vec_ok(dtype, {C, xps}, {x, u3, g, out});
-  DISPATCH_TV(dtype, v, scgate_fwd_kernel<T, NV><<<egrid((long)N * H * W * C / NV), 256, 0, st>>>((const T*)x, xps, (const T*)u3, (const T*)g, (T*)out, N, H, W, C, GH, GW));
-  return (int)hipGetLastError();
+  const bool v = vec_ok(vec_width(dtype), C, {xps}, {}, {x, u3, g, out});
+  return by_dtype_vec(dtype, v, kInvalid, [&](auto tag, auto nv) {
+    using T = typename decltype(tag)::type;
+    constexpr int NV = decltype(nv)::value;
+    return launch(scgate_fwd_kernel<T, NV>, vgrid((long)N * H * W * C / NV), stream, x, xps, u3, g, out, N, H, W, C, GH,
+        GW);
+  });
 }
 DMY_API int dmy_scgate_bwd(int dtype, const void* x, long xps, const void* u3, const void* g, const void* dout,
                            void* du3, void* dpre, long dpps, int accumulate, int N, int H, int W, int C, int GH, int GW,
                            void* stream) {
-  hipStream_t st = (hipStream_t)stream;
-  const bool v = vec_ok(dtype, {C, xps, dpps}, {x, u3, g, dout, du3, dpre});
-  DISPATCH_TV(dtype, v, scgate_bwd_kernel<T, NV><<<egrid((long)N * H * W * C / NV), 256, 0, st>>>((const T*)x, xps, (const T*)u3, (const T*)g, (const T*)dout, (T*)du3, (T*)dpre, dpps, accumulate, N, H, W, C, GH, GW));
-  return (int)hipGetLastError();
+  const bool v = vec_ok(vec_width(dtype), C, {xps, dpps}, {}, {x, u3, g, dout, du3, dpre});
+  return by_dtype_vec(dtype, v, kInvalid, [&](auto tag, auto nv) {
+    using T = typename decltype(tag)::type;
+    constexpr int NV = decltype(nv)::value;
+    return launch(scgate_bwd_kernel<T, NV>, vgrid((long)N * H * W * C / NV), stream, x, xps, u3, g, dout, du3, dpre,
+        dpps, accumulate, N, H, W, C, GH, GW);
+  });
 }
 DMY_API int dmy_ca_pool_fwd(int dtype, const void* x, long xps, void* y, int N, int H, int W, int C, void* stream) {
-  hipStream_t st = (hipStream_t)stream;
-  DISPATCH_T(dtype, ca_pool_fwd_kernel<T><<<egrid((long)N * (H + W) * C), 256, 0, st>>>((const T*)x, xps, (T*)y, N, H, W, C));
-  return (int)hipGetLastError();
+  return by_dtype(dtype, kInvalid, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    return launch(ca_pool_fwd_kernel<T>, vgrid((long)N * (H + W) * C), stream, x, xps, y, N, H, W, C);
+  });
 }
 DMY_API int dmy_ca_pool_bwd(int dtype, const void* dy, void* dx, long dxps, int accumulate, int N, int H, int W, int C,
                             void* stream) {
-  hipStream_t st = (hipStream_t)stream;
-  DISPATCH_T(dtype, ca_pool_bwd_kernel<T><<<egrid((long)N * H * W * C), 256, 0, st>>>((const T*)dy, (T*)dx, dxps, accumulate, N, H, W, C));
-  return (int)hipGetLastError();
+  return by_dtype(dtype, kInvalid, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    return launch(ca_pool_bwd_kernel<T>, vgrid((long)N * H * W * C), stream, dy, dx, dxps, accumulate, N, H, W, C);
+  });
 }
 DMY_API int dmy_ca_apply_fwd(int dtype, const void* x, long xps, const void* lh, const void* lw, void* out, long ops,
                              int N, int H, int W, int C, void* stream) {
-  hipStream_t st = (hipStream_t)stream;
-  DISPATCH_T(dtype, ca_apply_fwd_kernel<T><<<egrid((long)N * H * W * C), 256, 0, st>>>((const T*)x, xps, (const T*)lh, (const T*)lw, (T*)out, ops, N, H, W, C));
-  return (int)hipGetLastError();
+  return by_dtype(dtype, kInvalid, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    return launch(ca_apply_fwd_kernel<T>, vgrid((long)N * H * W * C), stream, x, xps, lh, lw, out, ops, N, H, W, C);
+  });
 }
 DMY_API int dmy_ca_apply_bwd(int dtype, const void* x, long xps, const void* lh, const void* lw, const void* dout,
                              long dps, void* dx, long dxps, void* dlh, void* dlw, int N, int H, int W, int C,
                              void* stream) {
   hipStream_t st = (hipStream_t)stream;
-  DISPATCH_T(dtype, ca_apply_bwd_dx_kernel<T><<<egrid((long)N * H * W * C), 256, 0, st>>>((const T*)x, xps, (const T*)lh, (const T*)lw, (const T*)dout, dps, (T*)dx, dxps, N, H, W, C));
-  DISPATCH_T(dtype, ca_apply_bwd_att_kernel<T><<<egrid((long)N * (H + W) * C), 256, 0, st>>>((const T*)x, xps, (const T*)lh, (const T*)lw, (const T*)dout, dps, (T*)dlh, (T*)dlw, N, H, W, C));
-  return (int)hipGetLastError();
+  return by_dtype(dtype, kInvalid, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    ca_apply_bwd_dx_kernel<T><<<vgrid((long)N * H * W * C), 256, 0, st>>>(
+        (const T*)x, xps, (const T*)lh, (const T*)lw, (const T*)dout, dps, (T*)dx, dxps, N, H, W, C);
+    ca_apply_bwd_att_kernel<T><<<vgrid((long)N * (H + W) * C), 256, 0, st>>>(
+        (const T*)x, xps, (const T*)lh, (const T*)lw, (const T*)dout, dps, (T*)dlh, (T*)dlw, N, H, W, C);
+    return (int)hipGetLastError();
+  });
 }
 // NCHW image (uint8 or fp32, H and W even) -> space-to-depth NHWC [N][H/2][W/2][Cs] T, channel
 // (dy * 2 + dx) * C + c = x[c][2 oy + dy][2 ox + dx] * scale, channels [4C, Cs) zero.  The k6 s2 p2 stem
@@ -1597,48 +1624,47 @@ __global__ void image_s2d_kernel(const S* __restrict__ x, T* __restrict__ y, int
 
 DMY_API int dmy_image_s2d(int dtype, int src_kind, const void* x, void* y, int N, int C, int H, int W, int Cs,
                           float scale, void* stream) {
-  const int VW = dtype ? 8 : 4;
-  if ((H | W) & 1 || Cs % VW || Cs < 4 * C || (((uintptr_t)y) & 15)) return (int)hipErrorInvalidValue;
-  hipStream_t st = (hipStream_t)stream;
-  const long n = (long)N * (H / 2) * (W / 2);
-  if (src_kind == 0) {
-    DISPATCH_T(dtype, image_s2d_kernel<uint8_t, T><<<egrid(n), 256, 0, st>>>((const uint8_t*)x, (T*)y, N, C, H, W, Cs, scale));
-  } else {
-    DISPATCH_T(dtype, image_s2d_kernel<float, T><<<egrid(n), 256, 0, st>>>((const float*)x, (T*)y, N, C, H, W, Cs, scale));
-  }
-  return (int)hipGetLastError();
+  if ((H | W) & 1 || Cs < 4 * C || !vec_ok(vec_width(dtype), Cs, {}, {}, {y})) return kInvalid;
+  const int g = vgrid((long)N * (H / 2) * (W / 2));
+  return by_dtype(dtype, kInvalid, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    if (src_kind == 0) image_s2d_kernel<uint8_t, T><<<g, 256, 0, (hipStream_t)stream>>>((const uint8_t*)x, (T*)y, N, C, H, W, Cs, scale);
+    else image_s2d_kernel<float, T><<<g, 256, 0, (hipStream_t)stream>>>((const float*)x, (T*)y, N, C, H, W, Cs, scale);
+    return (int)hipGetLastError();
+  });
 }
 // src_kind: 0 = uint8, 1 = fp32; output NHWC with pixel stride Cp >= C (zero-filled tail channels).  Cp must be a
 // whole number of 16-B vectors of the storage type (functional.vec_pad) and y 16-B aligned: hipErrorInvalidValue
 // otherwise
 DMY_API int dmy_nchw_to_nhwc(int dtype, int src_kind, const void* x, void* y, int N, int C, int H, int W, int Cp,
                              float scale, void* stream) {
-  if (Cp % (dtype ? 8 : 4) || Cp < C || (((uintptr_t)y) & 15)) return (int)hipErrorInvalidValue;
-  hipStream_t st = (hipStream_t)stream;
-  const long n = (long)N * H * W;
-  if (src_kind == 0) {
-    DISPATCH_T(dtype, nchw_to_nhwc_kernel<uint8_t, T><<<egrid(n), 256, 0, st>>>((const uint8_t*)x, (T*)y, N, C, H, W, Cp, scale));
-  } else {
-    DISPATCH_T(dtype, nchw_to_nhwc_kernel<float, T><<<egrid(n), 256, 0, st>>>((const float*)x, (T*)y, N, C, H, W, Cp, scale));
-  }
-  return (int)hipGetLastError();
+  if (Cp < C || !vec_ok(vec_width(dtype), Cp, {}, {}, {y})) return kInvalid;
+  const int g = vgrid((long)N * H * W);
+  return by_dtype(dtype, kInvalid, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    if (src_kind == 0) nchw_to_nhwc_kernel<uint8_t, T><<<g, 256, 0, (hipStream_t)stream>>>((const uint8_t*)x, (T*)y, N, C, H, W, Cp, scale);
+    else nchw_to_nhwc_kernel<float, T><<<g, 256, 0, (hipStream_t)stream>>>((const float*)x, (T*)y, N, C, H, W, Cp, scale);
+    return (int)hipGetLastError();
+  });
 }
 DMY_API int dmy_nhwc_to_nchw_f32(int dtype, const void* x, long xps, float* y, int N, int C, int H, int W,
                                  void* stream) {
-  hipStream_t st = (hipStream_t)stream;
-  DISPATCH_T(dtype, nhwc_to_nchw_kernel<T, float><<<egrid((long)N * C * H * W), 256, 0, st>>>((const T*)x, xps, y, N, C, H, W));
-  return (int)hipGetLastError();
+  return by_dtype(dtype, kInvalid, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    return launch(nhwc_to_nchw_kernel<T, float>, vgrid((long)N * C * H * W), stream, x, xps, y, N, C, H, W);
+  });
 }
 DMY_API int dmy_pointwise(int dtype, int op, int act, const void* a, const void* b, void* y, long n, float alpha,
                           void* stream) {
-  hipStream_t st = (hipStream_t)stream;
-  DISPATCH_T(dtype, pointwise_kernel<T><<<egrid(n), 256, 0, st>>>(op, act, (const T*)a, (const T*)b, (T*)y, n, alpha));
-  return (int)hipGetLastError();
+  return by_dtype(dtype, kInvalid, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    return launch(pointwise_kernel<T>, vgrid(n), stream, op, act, a, b, y, n, alpha);
+  });
 }
 // kinds: 0 f32, 1 bf16
 DMY_API int dmy_cast(int src_kind, int dst_kind, const void* x, void* y, long n, float scale, void* stream) {
   hipStream_t st = (hipStream_t)stream;
-  const int g = egrid(n);
+  const int g = vgrid(n);
   if (src_kind == 0 && dst_kind == 1) cast_kernel<float, bf16><<<g, 256, 0, st>>>((const float*)x, (bf16*)y, n, scale);
   else if (src_kind == 1 && dst_kind == 0) cast_kernel<bf16, float><<<g, 256, 0, st>>>((const bf16*)x, (float*)y, n, scale);
   else if (src_kind == 0) cast_kernel<float, float><<<g, 256, 0, st>>>((const float*)x, (float*)y, n, scale);

@@ -13,8 +13,7 @@
 // keeps bn.hip's row walk instead: a thread owns one channel vector, so its share of sum_m dout * y stays in registers;
 // the block's row groups are summed through LDS in a fixed order into one partial row per block, and dmy_reduce_rows
 // sums the rows in row order: bit-identical run to run.
-#include "common.h"
-#include <initializer_list>
+#include "launch.h"
 
 namespace {
 
@@ -149,63 +148,55 @@ __global__ void __launch_bounds__(256) layerscale_bwd_kernel(const T* __restrict
   }
 }
 
-inline bool al16(const void* p) { return p != nullptr && (((uintptr_t)p) & 15) == 0; }
-
-// 16-byte vectors everywhere: C and every pixel stride a whole number of vectors, bases aligned
-inline bool hor_ok(int dtype, long M, int C, std::initializer_list<long> strides, std::initializer_list<const void*> ps) {
-  const int VW = dtype ? 8 : 4;
-  if ((dtype != 0 && dtype != 1) || M < 1 || C < VW || C % VW) return false;
-  for (long s : strides)
-    if (s < C || s % VW) return false;
-  for (const void* p : ps)
-    if (!al16(p)) return false;
-  return true;
-}
-
-inline int vgrid(long n) { return grid_cap(ceil_div(n, 256), 16384); }
-
 }  // namespace
 
 DMY_API int dmy_gate_fwd(int dtype, const void* a, long aps, const void* b, long bps, void* y, long yps, long M, int C,
                          float scale, void* stream) {
-  if (!hor_ok(dtype, M, C, {aps, bps, yps}, {a, b, y})) return (int)hipErrorInvalidValue;
-  hipStream_t st = (hipStream_t)stream;
-  const int g = vgrid(M * (C / (dtype ? 8 : 4)));
-  if (dtype) gate_fwd_kernel<bf16><<<g, 256, 0, st>>>((const bf16*)a, aps, (const bf16*)b, bps, (bf16*)y, yps, M, C, scale);
-  else gate_fwd_kernel<float><<<g, 256, 0, st>>>((const float*)a, aps, (const float*)b, bps, (float*)y, yps, M, C, scale);
-  return (int)hipGetLastError();
+  const int VW = vec_width(dtype);
+  if (M < 1 || C < VW || !vec_ok(VW, C, {aps, bps, yps}, {a, b, y}) || !rows_fit(C, {aps, bps, yps}))
+    return kInvalid;
+  return by_dtype(dtype, kInvalid, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    return launch(gate_fwd_kernel<T>, vgrid(M * (C / VW)), stream, a, aps, b, bps, y, yps, M, C, scale);
+  });
 }
 
 DMY_API int dmy_gate_bwd(int dtype, const void* dy, long dps, const void* a, long aps, const void* b, long bps, void* da,
                          long daps, void* db, long dbps, long M, int C, float scale, void* stream) {
-  if (!hor_ok(dtype, M, C, {dps, aps, bps, daps, dbps}, {dy, a, b, da, db})) return (int)hipErrorInvalidValue;
-  hipStream_t st = (hipStream_t)stream;
-  const int g = vgrid(M * (C / (dtype ? 8 : 4)));
-  if (dtype) gate_bwd_kernel<bf16><<<g, 256, 0, st>>>((const bf16*)dy, dps, (const bf16*)a, aps, (const bf16*)b, bps, (bf16*)da, daps, (bf16*)db, dbps, M, C, scale);
-  else gate_bwd_kernel<float><<<g, 256, 0, st>>>((const float*)dy, dps, (const float*)a, aps, (const float*)b, bps, (float*)da, daps, (float*)db, dbps, M, C, scale);
-  return (int)hipGetLastError();
+  const int VW = vec_width(dtype);
+  if (M < 1 || C < VW || !vec_ok(VW, C, {dps, aps, bps, daps, dbps}, {dy, a, b, da, db}) ||
+      !rows_fit(C, {dps, aps, bps, daps, dbps}))
+    return kInvalid;
+  return by_dtype(dtype, kInvalid, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    return launch(gate_bwd_kernel<T>, vgrid(M * (C / VW)), stream, dy, dps, a, aps, b, bps, da, daps, db, dbps, M, C,
+        scale);
+  });
 }
 
 DMY_API int dmy_layerscale_fwd(int dtype, const void* x, long xps, const void* y, const float* gamma, void* out,
                                long ops, long M, int C, void* stream) {
-  if (!hor_ok(dtype, M, C, {xps, ops}, {x, y, out}) || !gamma) return (int)hipErrorInvalidValue;
-  hipStream_t st = (hipStream_t)stream;
-  const int g = vgrid(M * (C / (dtype ? 8 : 4)));
-  if (dtype) layerscale_fwd_kernel<bf16><<<g, 256, 0, st>>>((const bf16*)x, xps, (const bf16*)y, gamma, (bf16*)out, ops, M, C);
-  else layerscale_fwd_kernel<float><<<g, 256, 0, st>>>((const float*)x, xps, (const float*)y, gamma, (float*)out, ops, M, C);
-  return (int)hipGetLastError();
+  const int VW = vec_width(dtype);
+  if (M < 1 || C < VW || !vec_ok(VW, C, {xps, ops}, {x, y, out}) || !rows_fit(C, {xps, ops}) || !gamma)
+    return kInvalid;
+  return by_dtype(dtype, kInvalid, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    return launch(layerscale_fwd_kernel<T>, vgrid(M * (C / VW)), stream, x, xps, y, gamma, out, ops, M, C);
+  });
 }
 
 // one partial row per block: a block per 32 rows, capped at 2048
 DMY_API int dmy_layerscale_bwd_rows(long M) { return M < 1 ? 0 : grid_cap(ceil_div(M, 32), 2048); }
 
+// a row is at most 256 vectors (the kernel's thread mapping)
 DMY_API int dmy_layerscale_bwd(int dtype, const void* dout, long dps, const void* y, const float* gamma, void* dy,
                                long M, int C, float* part, void* stream) {
-  if (!hor_ok(dtype, M, C, {dps}, {dout, y, dy}) || C / (dtype ? 8 : 4) > 256 || !gamma || !part)
-    return (int)hipErrorInvalidValue;
-  hipStream_t st = (hipStream_t)stream;
-  const int g = dmy_layerscale_bwd_rows(M);
-  if (dtype) layerscale_bwd_kernel<bf16><<<g, 256, 0, st>>>((const bf16*)dout, dps, (const bf16*)y, gamma, (bf16*)dy, M, C, part);
-  else layerscale_bwd_kernel<float><<<g, 256, 0, st>>>((const float*)dout, dps, (const float*)y, gamma, (float*)dy, M, C, part);
-  return (int)hipGetLastError();
+  const int VW = vec_width(dtype);
+  if (M < 1 || C < VW || !vec_ok(VW, C, {dps}, {dout, y, dy}) || dps < C || C / VW > 256 || !gamma || !part)
+    return kInvalid;
+  return by_dtype(dtype, kInvalid, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    return launch(layerscale_bwd_kernel<T>, dmy_layerscale_bwd_rows(M), stream, dout, dps, y, gamma, dy, M, C, part);
+  });
 }
+

@@ -14,8 +14,7 @@
 // The three BN passes are bn.hip's bn_act_fwd_vec / bn_bwd_reduce_vec / bn_bwd_apply_vec with the SM-side address
 // replaced: same thread mapping (RowMap), same grids, same row order, the per-channel expressions of common.h's
 // act_fwd_n / act_grad_n, so each gives the bits of the plain pass composed with dmy_space_to_depth.
-#include "common.h"
-#include <initializer_list>
+#include "launch.h"
 
 namespace {
 
@@ -313,119 +312,112 @@ __global__ void __launch_bounds__(256) maxpool2_bwd_kernel(const T* __restrict__
   }
 }
 
-inline bool al16(const void* p) { return p != nullptr && (((uintptr_t)p) & 15) == 0; }
-
-// 16-byte vectors everywhere: C and every pixel stride a whole number of vectors, bases aligned, at most 256 vectors per
-// row (RowMap)
-inline bool spd_ok(int dtype, int C, std::initializer_list<long> strides, std::initializer_list<const void*> ps) {
-  const int VW = dtype ? 8 : 4;
-  if ((dtype != 0 && dtype != 1) || C < VW || C % VW || C / VW > 256) return false;
-  for (long s : strides)
-    if (s < C || s % VW) return false;
-  for (const void* p : ps)
-    if (!al16(p)) return false;
-  return true;
-}
-
-// grids of bn.hip's streaming passes (vec_grid_red / vec_grid_ew): the reduce capped at 2048 blocks (= partial rows),
-// the elementwise passes at 16384
-inline int row_grid(long M, int C, int VW, int cap) {
-  const int RB = 256 / (C / VW);
-  return grid_cap(ceil_div(M, (long)RB * 8), cap);
-}
-inline int vgrid(long n) { return grid_cap(ceil_div(n, 256), 16384); }
+// Besides the vector contract, at every call site: a row is 1..256 vectors (RowMap) and fits its stride; the SM side
+// holds 4 K channels per pixel; the argmax rows are stored 8 bytes at a time.  The grids are those of bn.hip's passes.
 
 }  // namespace
 
 DMY_API int dmy_bn_act_s2d_fwd(int dtype, const void* z, long zps, const float* scale, const float* shift, int act,
                                void* y, long yps, int N, int H, int W, int K, void* stream) {
-  if (N < 1 || H < 2 || W < 2 || ((H | W) & 1) || !spd_ok(dtype, K, {zps}, {z, y}) || !scale || !shift || yps < 4L * K ||
-      yps % (dtype ? 8 : 4))
-    return (int)hipErrorInvalidValue;
-  hipStream_t st = (hipStream_t)stream;
-  const int g = row_grid((long)N * H * W, K, dtype ? 8 : 4, 16384);
-  if (dtype) bn_act_s2d_fwd_kernel<bf16><<<g, 256, 0, st>>>((const bf16*)z, zps, scale, shift, act, (bf16*)y, yps, N, H, W, K);
-  else bn_act_s2d_fwd_kernel<float><<<g, 256, 0, st>>>((const float*)z, zps, scale, shift, act, (float*)y, yps, N, H, W, K);
-  return (int)hipGetLastError();
+  const int VW = vec_width(dtype);
+  if (N < 1 || H < 2 || W < 2 || ((H | W) & 1) || K < VW || K / VW > 256 || !vec_ok(VW, K, {zps, yps}, {z, y}) ||
+      zps < K || yps < 4L * K || !scale || !shift)
+    return kInvalid;
+  return by_dtype(dtype, kInvalid, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    return launch(bn_act_s2d_fwd_kernel<T>, row_grid((long)N * H * W, K, VW, kEwCap), stream, z, zps, scale, shift, act,
+        y, yps, N, H, W, K);
+  });
 }
 
 DMY_API int dmy_bn_bwd_reduce_s2d_rows(int dtype, long M, int K) {
-  const int VW = dtype ? 8 : 4;
+  const int VW = vec_width(dtype);
   if (M < 1 || K < VW || K % VW || K / VW > 256) return 0;
-  return row_grid(M, K, VW, 2048);
+  return row_grid(M, K, VW, kRedCap);
 }
 
 DMY_API int dmy_bn_bwd_reduce_s2d(int dtype, const void* z, long zps, const void* dy, long dps, const float* scale,
                                   const float* shift, const float* mean, const float* invstd, int act, int N, int H,
                                   int W, int K, float* pdb, float* pdg, void* stream) {
-  if (N < 1 || H < 2 || W < 2 || ((H | W) & 1) || !spd_ok(dtype, K, {zps}, {z, dy}) || !scale || !shift || !mean || !invstd ||
-      dps < 4L * K || dps % (dtype ? 8 : 4) || !pdb || !pdg)
-    return (int)hipErrorInvalidValue;
-  hipStream_t st = (hipStream_t)stream;
-  const int g = dmy_bn_bwd_reduce_s2d_rows(dtype, (long)N * H * W, K);
-  if (dtype) bn_bwd_reduce_s2d_kernel<bf16><<<g, 256, 0, st>>>((const bf16*)z, zps, (const bf16*)dy, dps, scale, shift, mean, invstd, act, N, H, W, K, pdb, pdg);
-  else bn_bwd_reduce_s2d_kernel<float><<<g, 256, 0, st>>>((const float*)z, zps, (const float*)dy, dps, scale, shift, mean, invstd, act, N, H, W, K, pdb, pdg);
-  return (int)hipGetLastError();
+  const int VW = vec_width(dtype);
+  if (N < 1 || H < 2 || W < 2 || ((H | W) & 1) || K < VW || K / VW > 256 || !vec_ok(VW, K, {zps, dps}, {z, dy}) ||
+      zps < K || dps < 4L * K || !scale || !shift || !mean || !invstd || !pdb || !pdg)
+    return kInvalid;
+  return by_dtype(dtype, kInvalid, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    return launch(bn_bwd_reduce_s2d_kernel<T>, dmy_bn_bwd_reduce_s2d_rows(dtype, (long)N * H * W, K), stream, z, zps,
+        dy, dps, scale, shift, mean, invstd, act, N, H, W, K, pdb, pdg);
+  });
 }
 
 DMY_API int dmy_bn_bwd_apply_s2d(int dtype, const void* z, long zps, const void* dy, long dps, const float* scale,
                                  const float* shift, const float* mean, const float* invstd, int act, const float* ca,
                                  const float* cb, const float* cc, void* dz, long dzps, int N, int H, int W, int K,
                                  void* stream) {
-  if (N < 1 || H < 2 || W < 2 || ((H | W) & 1) ||
-      !spd_ok(dtype, K, {zps, dzps}, {z, dy, dz}) || !scale || !shift || !mean || !invstd || !ca || !cb || !cc || dps < 4L * K ||
-      dps % (dtype ? 8 : 4))
-    return (int)hipErrorInvalidValue;
-  hipStream_t st = (hipStream_t)stream;
-  const int g = row_grid((long)N * H * W, K, dtype ? 8 : 4, 16384);
-  if (dtype) bn_bwd_apply_s2d_kernel<bf16><<<g, 256, 0, st>>>((const bf16*)z, zps, (const bf16*)dy, dps, scale, shift, mean, invstd, act, ca, cb, cc, (bf16*)dz, dzps, N, H, W, K);
-  else bn_bwd_apply_s2d_kernel<float><<<g, 256, 0, st>>>((const float*)z, zps, (const float*)dy, dps, scale, shift, mean, invstd, act, ca, cb, cc, (float*)dz, dzps, N, H, W, K);
-  return (int)hipGetLastError();
+  const int VW = vec_width(dtype);
+  if (N < 1 || H < 2 || W < 2 || ((H | W) & 1) || K < VW || K / VW > 256 ||
+      !vec_ok(VW, K, {zps, dzps, dps}, {z, dy, dz}) || !rows_fit(K, {zps, dzps}) || dps < 4L * K || !scale || !shift ||
+      !mean || !invstd || !ca || !cb || !cc)
+    return kInvalid;
+  return by_dtype(dtype, kInvalid, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    return launch(bn_bwd_apply_s2d_kernel<T>, row_grid((long)N * H * W, K, VW, kEwCap), stream, z, zps, dy, dps, scale,
+        shift, mean, invstd, act, ca, cb, cc, dz, dzps, N, H, W, K);
+  });
 }
 
 DMY_API int dmy_maxpool2_fwd(int dtype, const void* x, long xps, void* y, long yps, unsigned char* argmax, int N, int H,
                              int W, int C, void* stream) {
-  if (N < 1 || H < 2 || W < 2 || !spd_ok(dtype, C, {xps, yps}, {x, y}) || !argmax || ((uintptr_t)argmax & 7))
-    return (int)hipErrorInvalidValue;
-  hipStream_t st = (hipStream_t)stream;
-  const int g = vgrid((long)N * (H / 2) * (W / 2) * (C / (dtype ? 8 : 4)));
-  if (dtype) maxpool2_fwd_kernel<bf16, false><<<g, 256, 0, st>>>((const bf16*)x, xps, (bf16*)y, yps, argmax, nullptr, 0, N, H, W, C);
-  else maxpool2_fwd_kernel<float, false><<<g, 256, 0, st>>>((const float*)x, xps, (float*)y, yps, argmax, nullptr, 0, N, H, W, C);
-  return (int)hipGetLastError();
+  const int VW = vec_width(dtype);
+  if (N < 1 || H < 2 || W < 2 || C < VW || C / VW > 256 || !vec_ok(VW, C, {xps, yps}, {x, y}) ||
+      !rows_fit(C, {xps, yps}) || !argmax || ((uintptr_t)argmax & 7))
+    return kInvalid;
+  return by_dtype(dtype, kInvalid, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    return launch(maxpool2_fwd_kernel<T, false>, vgrid((long)N * (H / 2) * (W / 2) * (C / VW)), stream, x, xps, y, yps,
+        argmax, nullptr, 0, N, H, W, C);
+  });
 }
 
 DMY_API int dmy_maxpool2_bwd(int dtype, const void* dy, long dps, const unsigned char* argmax, void* dx, long dxps,
                              int accumulate, int N, int H, int W, int C, void* stream) {
-  if (N < 1 || H < 2 || W < 2 || !spd_ok(dtype, C, {dps, dxps}, {dy, dx}) || !argmax || ((uintptr_t)argmax & 7))
-    return (int)hipErrorInvalidValue;
-  hipStream_t st = (hipStream_t)stream;
-  const int g = vgrid((long)N * H * W * (C / (dtype ? 8 : 4)));
-  if (dtype) maxpool2_bwd_kernel<bf16, false><<<g, 256, 0, st>>>((const bf16*)dy, dps, argmax, nullptr, 0, (bf16*)dx, dxps, accumulate, N, H, W, C);
-  else maxpool2_bwd_kernel<float, false><<<g, 256, 0, st>>>((const float*)dy, dps, argmax, nullptr, 0, (float*)dx, dxps, accumulate, N, H, W, C);
-  return (int)hipGetLastError();
+  const int VW = vec_width(dtype);
+  if (N < 1 || H < 2 || W < 2 || C < VW || C / VW > 256 || !vec_ok(VW, C, {dps, dxps}, {dy, dx}) ||
+      !rows_fit(C, {dps, dxps}) || !argmax || ((uintptr_t)argmax & 7))
+    return kInvalid;
+  return by_dtype(dtype, kInvalid, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    return launch(maxpool2_bwd_kernel<T, false>, vgrid((long)N * H * W * (C / VW)), stream, dy, dps, argmax, nullptr, 0,
+        dx, dxps, accumulate, N, H, W, C);
+  });
 }
 
 DMY_API int dmy_spd_split_fwd(int dtype, const void* x, long xps, void* sm, long smps, void* mp, long mpps,
                               unsigned char* argmax, int N, int H, int W, int C, void* stream) {
-  if (N < 1 || H < 2 || W < 2 || ((H | W) & 1) || !spd_ok(dtype, C, {xps, mpps}, {x, sm, mp}) || smps < 4L * C ||
-      smps % (dtype ? 8 : 4) || !argmax || ((uintptr_t)argmax & 7))
-    return (int)hipErrorInvalidValue;
-  hipStream_t st = (hipStream_t)stream;
-  const int g = vgrid((long)N * (H / 2) * (W / 2) * (C / (dtype ? 8 : 4)));
-  if (dtype) maxpool2_fwd_kernel<bf16, true><<<g, 256, 0, st>>>((const bf16*)x, xps, (bf16*)mp, mpps, argmax, (bf16*)sm, smps, N, H, W, C);
-  else maxpool2_fwd_kernel<float, true><<<g, 256, 0, st>>>((const float*)x, xps, (float*)mp, mpps, argmax, (float*)sm, smps, N, H, W, C);
-  return (int)hipGetLastError();
+  const int VW = vec_width(dtype);
+  if (N < 1 || H < 2 || W < 2 || ((H | W) & 1) || C < VW || C / VW > 256 ||
+      !vec_ok(VW, C, {xps, mpps, smps}, {x, sm, mp}) || !rows_fit(C, {xps, mpps}) || smps < 4L * C || !argmax ||
+      ((uintptr_t)argmax & 7))
+    return kInvalid;
+  return by_dtype(dtype, kInvalid, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    return launch(maxpool2_fwd_kernel<T, true>, vgrid((long)N * (H / 2) * (W / 2) * (C / VW)), stream, x, xps, mp, mpps,
+        argmax, sm, smps, N, H, W, C);
+  });
 }
 
 DMY_API int dmy_spd_split_bwd(int dtype, const void* dsm, long dsmps, const void* dmp, long dmpps,
                               const unsigned char* argmax, void* dx, long dxps, int N, int H, int W, int C,
                               void* stream) {
-  if (N < 1 || H < 2 || W < 2 || ((H | W) & 1) || !spd_ok(dtype, C, {dmpps, dxps}, {dsm, dmp, dx}) || dsmps < 4L * C ||
-      dsmps % (dtype ? 8 : 4) || !argmax || ((uintptr_t)argmax & 7))
-    return (int)hipErrorInvalidValue;
-  hipStream_t st = (hipStream_t)stream;
-  const int g = vgrid((long)N * H * W * (C / (dtype ? 8 : 4)));
-  if (dtype) maxpool2_bwd_kernel<bf16, true><<<g, 256, 0, st>>>((const bf16*)dmp, dmpps, argmax, (const bf16*)dsm, dsmps, (bf16*)dx, dxps, 0, N, H, W, C);
-  else maxpool2_bwd_kernel<float, true><<<g, 256, 0, st>>>((const float*)dmp, dmpps, argmax, (const float*)dsm, dsmps, (float*)dx, dxps, 0, N, H, W, C);
-  return (int)hipGetLastError();
+  const int VW = vec_width(dtype);
+  if (N < 1 || H < 2 || W < 2 || ((H | W) & 1) || C < VW || C / VW > 256 ||
+      !vec_ok(VW, C, {dmpps, dxps, dsmps}, {dsm, dmp, dx}) || !rows_fit(C, {dmpps, dxps}) || dsmps < 4L * C || !argmax ||
+      ((uintptr_t)argmax & 7))
+    return kInvalid;
+  return by_dtype(dtype, kInvalid, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    return launch(maxpool2_bwd_kernel<T, true>, vgrid((long)N * H * W * (C / VW)), stream, dmp, dmpps, argmax, dsm,
+        dsmps, dx, dxps, 0, N, H, W, C);
+  });
 }
+

@@ -448,6 +448,29 @@ def prep_weight(w, dtype, need_t, Cp=None):
 VW = {torch.float32: 4, torch.bfloat16: 8}
 
 
+def vec_ok(dtype, chans=(), strides=(), tensors=()):
+    """The 16-byte vector contract of the streaming kernels (csrc/launch.h vec_ok): channel counts and pixel strides in
+    multiples of 8 (bf16) / 4 (fp32), 16-byte aligned bases.  False: the caller falls back (vec_view) or refuses."""
+    vw = VW[dtype]
+    return not (any(c % vw for c in chans) or any(s % vw for s in strides) or any(t.data_ptr() % 16 for t in tensors))
+
+
+def vec_check(what, dtype, chans=(), strides=(), tensors=(), max_vecs=None):
+    """vec_ok for a kernel with no scalar path: NotImplementedError where it fails (or a pixel has over max_vecs vectors)"""
+    if not vec_ok(dtype, chans, strides, tensors) or (max_vecs and any(c // VW[dtype] > max_vecs for c in chans)):
+        raise NotImplementedError(f'{what}: channel counts {list(chans)} / pixel strides {list(strides)} must be '
+                                  f'multiples of {VW[dtype]} for {dtype} and every tensor 16-byte aligned'
+                                  + (f', at most {max_vecs} vectors per pixel' if max_vecs else ''))
+
+
+def vec_view(t):
+    """(t', ps) as pixel_stride, copied dense when the view is not 16-byte-vector addressable (an odd slice offset)"""
+    t, ps = pixel_stride(t)
+    if not vec_ok(t.dtype, (), [ps], [t]):
+        t, ps = pixel_stride(t.contiguous(memory_format=CL))
+    return t, ps
+
+
 def vec_pad(C, dtype):
     """C rounded up to a whole number of 16-byte vectors of dtype"""
     return -(-C // VW[dtype]) * VW[dtype]
@@ -1025,10 +1048,8 @@ class ConvBNActFn(torch.autograd.Function):
     def backward(ctx, dy):
         g, spec = ctx.g, ctx.spec
         x, wt, z, *bnt = ctx.saved_tensors
-        dy, dps = pixel_stride(dy.to(z.dtype))
+        dy, dps = (vec_view if ctx.spd else pixel_stride)(dy.to(z.dtype))  # the SM passes read dy as 16-byte vectors
         K, dev, dt = g.K, dy.device, dcode(dy)
-        if ctx.spd and (dps % VW[dy.dtype] or dy.data_ptr() % 16):  # the SM passes read dy as 16-byte vectors
-            dy, dps = pixel_stride(dy.contiguous(memory_format=CL))
         dbias = dgamma = dbeta = fused = None
         bias_in_wgrad = _dw_bias_in_wgrad(ctx)
         if spec.bn is not None:
@@ -1146,11 +1167,9 @@ class ConvActBNFn(torch.autograd.Function):
         if g.K % VW[x.dtype] or g.s2d or g.Cp != g.C:
             raise NotImplementedError(f'conv -> act -> BN takes whole 16-byte vectors: output channels multiples of '
                                       f'{VW[x.dtype]} for {x.dtype}, got {g.K}')
-        res, rps = pixel_stride(res) if res is not None else (None, 0)
-        if res is not None and (rps % VW[x.dtype] or res.data_ptr() % 16):
-            res, rps = pixel_stride(res.contiguous(memory_format=CL))
+        res, rps = vec_view(res) if res is not None else (None, 0)
         out, yps = out_view(out and out[0], (g.N, g.K, g.OH, g.OW), x)
-        if out is not None and (yps % VW[x.dtype] or out.data_ptr() % 16):
+        if out is not None and not vec_ok(x.dtype, (), [yps], [out]):
             out = None
         y = out if out is not None else new_act(g.N, g.K, g.OH, g.OW, x)
         yps = g.K if out is None else yps
@@ -1169,9 +1188,7 @@ class ConvActBNFn(torch.autograd.Function):
     def backward(ctx, dy):
         g, spec = ctx.g, ctx.spec
         x, wt, z, scale, mean, invstd = ctx.saved_tensors
-        dy, dps = pixel_stride(dy.to(z.dtype))
-        if dps % VW[dy.dtype] or dy.data_ptr() % 16:
-            dy, dps = pixel_stride(dy.contiguous(memory_format=CL))
+        dy, dps = vec_view(dy.to(z.dtype))
         K, M, dev, dt = g.K, g.M, dy.device, dcode(dy)
         dbias = dgamma = dbeta = None
         P = call('dmy_bn_partial_rows', M)
@@ -1254,26 +1271,11 @@ def maxpool_chain3(x, k, outs=(None, None, None)):
         ys = [v for v, _ in views]
     else:
         ys, yps = [new_act(N, C, H, W, x) for _ in range(3)], C
-    if C % vw or xps % vw or yps % vw or N * (C // vw) >= 65536 or any(t.data_ptr() % 16 for t in [x] + ys):
+    if not vec_ok(x.dtype, [C], [xps, yps], [x] + ys) or N * (C // vw) >= 65536:
         return None
     call('dmy_maxpool_chain3_fwd', dcode(x), ptr(x), xps, ptr(ys[0]), ptr(ys[1]), ptr(ys[2]), yps, N, H, W, C, k,
          stream())
     return tuple(ys)
-
-
-def _spd_vec(what, C, dtype):
-    if C % VW[dtype] or C // VW[dtype] > 256:
-        raise NotImplementedError(f'{what} (csrc/spd.hip) takes whole 16-byte vectors, at most 256 per pixel: channels '
-                                  f'multiples of {VW[dtype]} for {dtype}, got {C}')
-
-
-def _vec_addressable(t):
-    """(t', ps) as pixel_stride, copied dense when the view is not 16-byte-vector addressable (an odd slice offset)"""
-    t, ps = pixel_stride(t)
-    if ps % VW[t.dtype] or t.data_ptr() % 16:
-        t = t.contiguous(memory_format=CL)
-        ps = t.shape[1]
-    return t, ps
 
 
 class MaxPool2Fn(torch.autograd.Function):
@@ -1283,9 +1285,9 @@ class MaxPool2Fn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, sink=None):
         dcode(x)
-        x, xps = _vec_addressable(x)
+        x, xps = vec_view(x)
         N, C, H, W = x.shape
-        _spd_vec('the 2 x 2 max pool', C, x.dtype)
+        vec_check('the 2 x 2 max pool (csrc/spd.hip)', x.dtype, [C], max_vecs=256)
         if H < 2 or W < 2:
             raise ValueError(f'MaxPool2d(2, 2) needs a map of at least 2 x 2, got {H}x{W}')
         y = new_act(N, C, H // 2, W // 2, x)
@@ -1299,7 +1301,7 @@ class MaxPool2Fn(torch.autograd.Function):
     def backward(ctx, dy):
         (arg,) = ctx.saved_tensors
         N, C, H, W = ctx.shape
-        dy, dps = _vec_addressable(dy)
+        dy, dps = vec_view(dy)
         buf, bps, acc = sink_target(ctx.sink, N, C, H, W, dy)
         call('dmy_maxpool2_bwd', dcode(dy), ptr(dy), dps, ptr(arg), ptr(buf), bps, acc, N, H, W, C, stream())
         return sink_result(ctx.sink, buf), None
@@ -1313,10 +1315,10 @@ class SpdSplitFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, out=None):
         dcode(x)
-        x, xps = _vec_addressable(x)
+        x, xps = vec_view(x)
         N, C, H, W = x.shape
         even_hw(H, W, 'SM / DMMConv2')
-        _spd_vec('the SM / MP split', C, x.dtype)
+        vec_check('the SM / MP split (csrc/spd.hip)', x.dtype, [C], max_vecs=256)
         sm, smps = out_view(out and out[0], (N, 4 * C, H // 2, W // 2), x)
         if sm is None:
             sm, smps = new_act(N, 4 * C, H // 2, W // 2, x), 4 * C
@@ -1331,8 +1333,8 @@ class SpdSplitFn(torch.autograd.Function):
     def backward(ctx, dsm, dmp):
         (arg,) = ctx.saved_tensors
         N, C, H, W = ctx.shape
-        dsm, dsps = _vec_addressable(dsm)
-        dmp, dmps = _vec_addressable(dmp)
+        dsm, dsps = vec_view(dsm)
+        dmp, dmps = vec_view(dmp)
         dx = new_act(N, C, H, W, dsm)
         call('dmy_spd_split_bwd', dcode(dsm), ptr(dsm), dsps, ptr(dmp), dmps, ptr(arg), ptr(dx), C, N, H, W, C, stream())
         return dx, None
@@ -1431,9 +1433,7 @@ class ConcatFn(torch.autograd.Function):
             x, xps = pixel_stride(x)
             g, gps, acc = sink_target(sinks[i], N, C, H, W, dy)
             sl = dy[:, c0:c0 + C]
-            vw = 8 if dy.dtype == torch.bfloat16 else 4
-            if C % vw == 0 and dps % vw == 0 and gps % vw == 0 and xps % vw == 0 and \
-                    all(t.data_ptr() % 16 == 0 for t in (sl, g, x)):  # one pass over the dy slice
+            if vec_ok(dy.dtype, [C], [dps, gps, xps], [sl, g, x]):  # one pass over the dy slice
                 call('dmy_slice_copy_dot', dcode(dy), ptr(sl), dps, ptr(g), gps, ptr(x), xps, M, C, ptr(w), i, len(xs),
                      float(ctx.eps), acc, ptr(part[i]), stream())
             else:
@@ -2033,15 +2033,6 @@ class PixScaleFn(torch.autograd.Function):
 
 # ------------------------------------------------------------------ adaptive-fusion necks (csrc/adapt.hip)
 
-def _adapt_check(what, dtype, chans, strides, tensors):
-    """the adapt kernels move whole 16-byte vectors: channel counts and pixel strides in multiples of 8 (bf16) / 4
-    (fp32), 16-byte aligned bases; there is no scalar path"""
-    vw = VW[dtype]
-    if any(c % vw for c in chans) or any(s % vw for s in strides) or any(t.data_ptr() % 16 for t in tensors):
-        raise NotImplementedError(f'{what}: channel counts {list(chans)} / pixel strides {list(strides)} must be '
-                                  f'multiples of {vw} for {dtype} and every tensor 16-byte aligned')
-
-
 def _lv3(xs, with_c=True):
     """(ptr, pixel stride[, channels]) argument triples of up to three levels, padded with nulls"""
     out = []
@@ -2072,7 +2063,7 @@ class AdaptGateFn(torch.autograd.Function):
             raise NotImplementedError('AdaptConcat: 16 level-map channels per level (rfb=False)')
         M, Ct = N * H * Wd, sum(chans)
         y = new_act(N, Ct, H, Wd, wm)
-        _adapt_check('AdaptConcat', wm.dtype, chans, [ps for _, ps in xs] + [wmps], [x for x, _ in xs] + [wm])
+        vec_check('AdaptConcat', wm.dtype, chans, [ps for _, ps in xs] + [wmps], [x for x, _ in xs] + [wm])
         a = f32(M * L, wm.device)
         Wc, bc = W.detach().contiguous(), b.detach().contiguous()
         call('dmy_adapt_gate_fwd', dcode(wm), L, *_lv3(xs), ptr(wm), wmps, ptr(Wc), ptr(bc), ptr(y), Ct, ptr(a), M,
@@ -2094,7 +2085,7 @@ class AdaptGateFn(torch.autograd.Function):
         sinks = ctx.sinks or [None] * L
         tg = [sink_target(sinks[l], N, x.shape[1], H, Wd, dy) for l, (x, _) in enumerate(xs)]
         acc = sum(t[2] << l for l, t in enumerate(tg))
-        _adapt_check('AdaptConcat backward', wm.dtype, [], [dps] + [t[1] for t in tg], [dy] + [t[0] for t in tg])
+        vec_check('AdaptConcat backward', wm.dtype, [], [dps] + [t[1] for t in tg], [dy] + [t[0] for t in tg])
         dwm = new_act(N, 16 * L, H, Wd, wm)
         nb = call('dmy_adapt_gate_blocks', dcode(wm), M, Ct, L)
         pdw, pdb = f32(nb * L * 16 * L, dev), f32(nb * L, dev)
@@ -2126,7 +2117,7 @@ class AdaptAddFn(torch.autograd.Function):
         xs = [pixel_stride(x) for x in xs]
         x0 = xs[0][0]
         N, C, H, Wd = x0.shape
-        _adapt_check('Adapt_Add', x0.dtype, [C], [ps for _, ps in xs], [x for x, _ in xs])
+        vec_check('Adapt_Add', x0.dtype, [C], [ps for _, ps in xs], [x for x, _ in xs])
         y = new_act(N, C, H, Wd, x0)
         wc = w.detach().contiguous()
         call('dmy_adapt_add_fwd', dcode(x0), n, *_lv3(xs, False), ptr(wc), float(eps), ptr(y), C, N * H * Wd, C,
@@ -2146,7 +2137,7 @@ class AdaptAddFn(torch.autograd.Function):
         sinks = ctx.sinks or [None] * n
         tg = [sink_target(sinks[i], N, C, H, Wd, dy) for i in range(n)]
         acc = sum(t[2] << i for i, t in enumerate(tg))
-        _adapt_check('Adapt_Add backward', dy.dtype, [], [dps] + [t[1] for t in tg], [dy] + [t[0] for t in tg])
+        vec_check('Adapt_Add backward', dy.dtype, [], [dps] + [t[1] for t in tg], [dy] + [t[0] for t in tg])
         nb = call('dmy_dot_partial_blocks', M, C)
         part = f32(n * nb, dy.device)
         dxa = []
@@ -2240,14 +2231,6 @@ class SplitFn(torch.autograd.Function):
         return sink.tick(), None, None, None
 
 
-def _hor_check(what, dtype, C, strides, tensors):
-    """the hor.hip kernels move whole 16-byte vectors (as _adapt_check)"""
-    vw = VW[dtype]
-    if C % vw or any(s % vw for s in strides) or any(t.data_ptr() % 16 for t in tensors):
-        raise NotImplementedError(f'{what}: {C} channels / pixel strides {list(strides)} must be multiples of {vw} for '
-                                  f'{dtype} and every tensor 16-byte aligned')
-
-
 def _write_target(sink, N, C, H, W, like):
     """-> (buffer, pixel stride, finish) for a backward kernel that writes but cannot accumulate: the sink's buffer
     when this is its first contribution (or a SliceSink part), else a fresh tensor that finish() adds into the sink"""
@@ -2274,7 +2257,7 @@ class GateMulFn(torch.autograd.Function):
         y, yps = out_view(out and out[0], a.shape, a)
         if y is None:
             y, yps = new_act(N, C, H, W, a), C
-        _hor_check('GateMulFn', a.dtype, C, [aps, bps, yps], [a, b, y])
+        vec_check('GateMulFn', a.dtype, [C], [aps, bps, yps], [a, b, y])
         call('dmy_gate_fwd', dcode(a), ptr(a), aps, ptr(b), bps, ptr(y), yps, N * H * W, C, float(scale), stream())
         ctx.save_for_backward(a, b)
         ctx.ps, ctx.scale, ctx.asink, ctx.bsink = (aps, bps), float(scale), asink, bsink
@@ -2288,7 +2271,7 @@ class GateMulFn(torch.autograd.Function):
         dy, dps = pixel_stride(dy.to(a.dtype))
         da, daps, fa = _write_target(ctx.asink, N, C, H, W, a)
         db, dbps, fb = _write_target(ctx.bsink, N, C, H, W, a)
-        _hor_check('GateMulFn backward', a.dtype, C, [dps, daps, dbps], [dy, da, db])
+        vec_check('GateMulFn backward', a.dtype, [C], [dps, daps, dbps], [dy, da, db])
         call('dmy_gate_bwd', dcode(a), ptr(dy), dps, ptr(a), aps, ptr(b), bps, ptr(da), daps, ptr(db), dbps, N * H * W,
              C, ctx.scale, stream())
         return fa(), fb(), None, None, None, None
@@ -2312,7 +2295,7 @@ class LayerScaleAddFn(torch.autograd.Function):
         o, ops = out_view(out and out[0], x.shape, x)
         if o is None:
             o, ops = new_act(N, C, H, W, x), C
-        _hor_check('LayerScaleAddFn', x.dtype, C, [xps, ops], [x, y, o])
+        vec_check('LayerScaleAddFn', x.dtype, [C], [xps, ops], [x, y, o])
         call('dmy_layerscale_fwd', dcode(x), ptr(x), xps, ptr(y), ptr(gm), ptr(o), ops, N * H * W, C, stream())
         ctx.save_for_backward(y, gm)
         ctx.xsink = xsink
@@ -2324,7 +2307,7 @@ class LayerScaleAddFn(torch.autograd.Function):
         N, C, H, W = y.shape
         M, dev = N * H * W, y.device
         dout, dps = pixel_stride(dout.to(y.dtype))
-        _hor_check('LayerScaleAddFn backward', y.dtype, C, [dps], [dout])
+        vec_check('LayerScaleAddFn backward', y.dtype, [C], [dps], [dout])
         if C // VW[y.dtype] > 256:
             raise NotImplementedError(f'LayerScaleAddFn backward: {C} channels, at most {256 * VW[y.dtype]}')
         dy = new_act(N, C, H, W, y)
