@@ -73,6 +73,10 @@ SIGNATURES = {
     'dmy_augment_batch': [P, I, P, I, I, P],
     'dmy_mosaic_desc_bytes': [],
     'dmy_mosaic_compose': [P, I, I, P],
+    # autoshape.hip
+    'dmy_letterbox_desc_bytes': [],
+    'dmy_letterbox_batch': [I, P, P, I, P, I, I, I, I, F, P],
+    'dmy_scale_boxes': [P, P, P, P, P, P, I, I, P],
     'dmy_fp8_quant_ws_elems': [],
     'dmy_fp8_quant': [P, L, I, L, P, P, P],
     'dmy_conv_wprep_fp8': [P, P, P, I, I, I, I, P],

@@ -7,15 +7,26 @@ forward() runs the gfx950 kernels through dmayolo.functional; there is no CPU pa
 
 Activation tensors are NHWC (torch.channels_last) in the model's storage dtype.
 """
+import ctypes
+import functools
+import logging
 import math
 import os
 import weakref
+from copy import copy
+from pathlib import Path
 
+import numpy as np
 import torch
 import torch.nn as nn
 
 from .. import functional as Fn
 from ..functional import ACT_NONE, ACT_SILU, ACT_HARDSWISH, ACT_SIGMOID, ACT_GELU, ACT_RELU, ACT_LEAKY
+from ..functional import call, ptr, stream
+from ..utils.general import make_divisible, nms_padded, xyxy2xywh
+from ..utils.torch_utils import time_sync
+
+_LOG = logging.getLogger('dmayolo')
 
 __all__ = ['autopad', 'Conv', 'DWConv', 'GhostConv', 'GhostBottleneck', 'C3Ghost', 'Bottleneck', 'C3', 'SPPF', 'SPPFCSPC', 'SCConv', 'CoorAttention', 'CA',
            'CABottleneck', 'C3CA', 'Concat', 'AdConcat2', 'AdConcat3', 'AdaptConcat', 'Adapt_Add2', 'Adapt_Add3', 'AdaptADD',
@@ -1006,3 +1017,272 @@ class C3TR(C3):
         super().__init__(c1, c2, n, shortcut, g, e)
         c_ = int(c2 * e)
         self.m = TransformerBlock(c_, c_, 4, n)
+
+
+# ------------------------------------------------------------------ AutoShape (models/common.py:701-891)
+
+# one image of dmy_letterbox_batch (csrc/autoshape.hip LetterboxDesc; sizeof = dmy_letterbox_desc_bytes)
+LETTERBOX_DESC = np.dtype([('src', '<u8'), ('xt', '<u8'), ('yt', '<u8'), ('H0', '<i4'), ('W0', '<i4'), ('h', '<i4'),
+                           ('w', '<i4'), ('top', '<i4'), ('left', '<i4'), ('swap', '<i4'), ('pad', '<i4')])
+
+
+def autoshape_geometry(shapes, size, stride):
+    """Host geometry of AutoShape.forward (models/common.py:769-775, 790) for images of `shapes` = [(H0, W0), ...]:
+    (shape1, [(h, w, top, left, gain, (pad_x, pad_y)) per image]).  shape1 is the batch's inference shape; (h, w) the
+    unpadded size and (top, left) the border letterbox(im, new_shape=shape1, auto=False) gives the image
+    (utils/augmentations.py:92-123); gain and pad are what scale_coords(shape1, ., (H0, W0)) computes, in double."""
+    shape1 = [[y * (size / max(s)) for y in s] for s in shapes]
+    shape1 = [make_divisible(x, stride) for x in np.stack(shape1, 0).max(0)]
+    geo = []
+    for H0, W0 in shapes:
+        r = min(shape1[0] / H0, shape1[1] / W0)
+        w, h = int(round(W0 * r)), int(round(H0 * r))
+        dw, dh = (shape1[1] - w) / 2, (shape1[0] - h) / 2
+        top, left = int(round(dh - 0.1)), int(round(dw - 0.1))
+        gain = min(shape1[0] / H0, shape1[1] / W0)
+        geo.append((h, w, top, left, gain, ((shape1[1] - W0 * gain) / 2, (shape1[0] - H0 * gain) / 2)))
+    return shape1, geo
+
+
+@functools.lru_cache(maxsize=64)
+def _resize_table(dst, src):
+    from ..augment import _resize_table as table
+    return table(dst, src)
+
+
+def letterbox_batch(imgs, shape1, geo, dtype, s2d, device, swap=False, stage=None):
+    """The stem input of a batch of decoded images (uint8 HWC, 3 channels, C-contiguous numpy arrays), letterboxed to
+    `shape1` with `geo` (autoshape_geometry) by ONE dmy_letterbox_batch launch: `dtype` in NHWC storage, space-to-depth
+    (`_dmy_s2d`, as Fn.image_s2d) or channel-padded (`_dmy_cpad`, as Model.to_input's ToNHWC).  The images, their
+    resize tables and the descriptors travel in one non-blocking copy from a pinned staging buffer (`stage`, a
+    one-element list that keeps it between calls)."""
+    assert call('dmy_letterbox_desc_bytes') == LETTERBOX_DESC.itemsize, 'LetterboxDesc layout mismatch'
+    n, (OH, OW) = len(imgs), shape1
+    parts, total = [], 0  # (offset, uint8 view) of everything the kernel reads
+
+    def put(a):
+        nonlocal total
+        off = -(-total // 16) * 16
+        parts.append((off, a.reshape(-1).view(np.uint8)))
+        total = off + a.nbytes
+        return off
+
+    d = np.zeros(n, dtype=LETTERBOX_DESC)
+    for k, (im, (h, w, top, left, _, _)) in enumerate(zip(imgs, geo)):
+        if im.dtype != np.uint8 or im.ndim != 3 or im.shape[2] != 3:
+            raise TypeError(f'image {k}: the letterbox kernel takes uint8 HWC images of 3 channels, got {im.dtype} '
+                            f'{im.shape}')
+        H0, W0 = im.shape[:2]
+        d[k]['src'], d[k]['xt'], d[k]['yt'] = put(np.ascontiguousarray(im)), put(_resize_table(w, W0)), \
+            put(_resize_table(h, H0))
+        d[k]['H0'], d[k]['W0'], d[k]['h'], d[k]['w'], d[k]['top'], d[k]['left'] = H0, W0, h, w, top, left
+        d[k]['swap'] = int(bool(swap))
+    doff = -(-total // 16) * 16
+    total = doff + d.nbytes
+    stage = [None] if stage is None else stage
+    if stage[0] is None or stage[0][0].numel() < total:
+        stage[0] = (torch.empty(max(total, 1 << 20), dtype=torch.uint8, pin_memory=True), torch.cuda.Event())
+    pinned, copied = stage[0]
+    copied.synchronize()  # the previous batch's copy has left the buffer
+    dev = torch.empty(total, dtype=torch.uint8, device=device)
+    base, host = dev.data_ptr(), pinned.numpy()
+    for f in ('src', 'xt', 'yt'):
+        d[f] += base
+    for off, a in parts:
+        host[off:off + a.size] = a
+    host[doff:total] = d.view(np.uint8)
+    dev.copy_(pinned[:total], non_blocking=True)
+    copied.record()
+    if s2d:
+        Cs = Fn.vec_pad(12, dtype)
+        buf = torch.empty((n, Cs, OH // 2, OW // 2), dtype=dtype, device=device, memory_format=Fn.CL)
+    else:
+        Cs = Fn.vec_pad(3, dtype)
+        buf = torch.empty((n, Cs, OH, OW), dtype=dtype, device=device, memory_format=Fn.CL)
+    call('dmy_letterbox_batch', Fn.DT[dtype], ctypes.c_void_p(base + doff), ctypes.c_void_p(pinned.data_ptr() + doff),
+         n, ptr(buf), OH, OW, int(bool(s2d)), Cs, 1.0 / 255.0, stream())
+    if s2d:
+        buf._dmy_s2d = 3
+        return buf
+    y = buf[:, :3] if Cs != 3 else buf
+    y._dmy_cpad = Cs
+    return y
+
+
+def scale_boxes(out, counts, geo, shapes):
+    """scale_coords (utils/general.py:605-617) of every image's rows of the padded NMS buffer `out`
+    (nimg, max_det, 6), in place, plus the Detections conversions (models/common.py:805-808), by ONE dmy_scale_boxes
+    launch: -> (xywh, xyxyn, xywhn), buffers of out's shape of which the first counts[b] rows of image b are written"""
+    nimg, max_det = out.shape[:2]
+    g = np.empty(6 * nimg, dtype=np.float32)  # [gain, pad_x, pad_y, w0, h0] per image, then the int32 keep counts
+    g[:5 * nimg] = [v for (_, _, _, _, gain, pad), (h0, w0) in zip(geo, shapes) for v in (gain, pad[0], pad[1], w0, h0)]
+    g[5 * nimg:].view(np.int32)[:] = counts
+    gd = torch.from_numpy(g).to(out.device)
+    extra = torch.empty((3,) + tuple(out.shape), dtype=torch.float32, device=out.device)
+    call('dmy_scale_boxes', ptr(out), ctypes.c_void_p(gd.data_ptr() + 20 * nimg), ptr(gd), ptr(extra[0]),
+         ptr(extra[1]), ptr(extra[2]), nimg, max_det, stream())
+    return extra[0], extra[1], extra[2]
+
+
+class AutoShape(nn.Module):
+    """models/common.py:701-793: input-robust wrapper -- raw images in, Detections out.  The host computes geometry
+    and resize tables only; letterbox, / 255, layout and cast are one dmy_letterbox_batch launch, the mapping of the
+    boxes back to each image one dmy_scale_boxes launch (csrc/autoshape.hip).
+
+    Accepted inputs: a numpy uint8 array (HWC; CHW when shape[0] < 5; 2-D grey; extra channels dropped), a PIL image,
+    a str / Path file name (decoded through PIL with the EXIF orientation applied), or a list of them; a torch.Tensor
+    goes straight to the model.  An http(s) URI raises NotImplementedError (the project has no network client), a
+    non-uint8 array TypeError."""
+    conf = 0.25  # NMS confidence threshold
+    iou = 0.45  # NMS IoU threshold
+    classes = None  # (optional list) filter by class
+    multi_label = False  # NMS multiple labels per box
+    max_det = 1000  # maximum number of detections per image
+
+    def __init__(self, model):
+        super().__init__()
+        self.model = model.eval()
+        self._stage = [None]  # pinned staging buffer of letterbox_batch, kept between calls
+
+    def __getstate__(self):
+        state = dict(self.__dict__)
+        state['_stage'] = [None]  # a copy or a pickle of the wrapper gets a staging buffer of its own
+        return state
+
+    def autoshape(self):
+        _LOG.info('AutoShape already enabled, skipping... ')
+        return self
+
+    def _prepare(self, imgs):
+        """models/common.py:756-773: -> (n, images as contiguous uint8 HWC RGB arrays, file names)"""
+        from PIL import Image, ImageOps
+        n, imgs = (len(imgs), list(imgs)) if isinstance(imgs, (list, tuple)) else (1, [imgs])
+        files = []
+        for i, im in enumerate(imgs):
+            f = f'image{i}'
+            if isinstance(im, (str, Path)):
+                if str(im).startswith('http'):
+                    raise NotImplementedError(f'{im}: fetching an image over the network is not supported, pass a '
+                                              'local file or a decoded image')
+                from ..data import _read_bgr
+                im, f = _read_bgr(str(im), rgb=True), im
+            elif isinstance(im, Image.Image):
+                im, f = np.asarray(ImageOps.exif_transpose(im)), getattr(im, 'filename', f) or f
+            elif not isinstance(im, np.ndarray):
+                raise TypeError(f'image {i}: expected a numpy array, a PIL image or a file name, got {type(im).__name__}')
+            files.append(Path(f).with_suffix('.jpg').name)
+            if im.shape[0] < 5:  # image in CHW
+                im = im.transpose((1, 2, 0))
+            im = im[..., :3] if im.ndim == 3 else np.tile(im[..., None], 3)
+            imgs[i] = np.ascontiguousarray(im)
+        return n, imgs, files
+
+    @torch.no_grad()
+    def forward(self, imgs, size=640, augment=False, profile=False):
+        t = [time_sync()]
+        p = next(self.model.parameters())
+        if isinstance(imgs, torch.Tensor):
+            return self.model(imgs.to(p.device), augment, profile)
+        if p.device.type != 'cuda':
+            raise RuntimeError('AutoShape runs on the GPU: move the model there first (there is no CPU path)')
+        n, imgs, files = self._prepare(imgs)
+        m = self.model
+        shapes = [im.shape[:2] for im in imgs]
+        shape1, geo = autoshape_geometry(shapes, size, int(getattr(self, 'stride', m.stride).max()))
+        if augment:
+            # the augmented forward resamples the NCHW image itself: hand it the letterboxed batch as fp32 planes
+            # (level * 1/255, the value its own uint8 path forms per tap)
+            x = letterbox_batch(imgs, shape1, geo, torch.float32, False, p.device, stage=self._stage).contiguous()
+        else:
+            s2d = m._s2d_stem(torch.empty((n, 3, *shape1), device='meta'))
+            x = letterbox_batch(imgs, shape1, geo, m.act_dtype, s2d, p.device, stage=self._stage)
+        t.append(time_sync())
+        y = m(x, augment, profile)[0]
+        t.append(time_sync())
+        out, pred = nms_padded(y, self.conf, iou_thres=self.iou, classes=self.classes, multi_label=self.multi_label,
+                               max_det=self.max_det)
+        xywh, xyxyn, xywhn = scale_boxes(out, [q.shape[0] for q in pred], geo, shapes)
+        extra = [[b[i, :q.shape[0]] for i, q in enumerate(pred)] for b in (xywh, xyxyn, xywhn)]
+        t.append(time_sync())
+        return Detections(imgs, pred, files, t, getattr(self, 'names', m.names), torch.Size((n, 3, *shape1)), *extra)
+
+
+class Detections:
+    """models/common.py:795-891: the results of one AutoShape call.  `pred` / `xyxy` are the per-image (k, 6) rows
+    (xyxy pixels of the original image, conf, cls), `xywh` the centre form, `xyxyn` / `xywhn` those divided by the
+    image's (w, h, w, h); `t` is ms per image of pre-process / inference / NMS.  AutoShape hands over the converted
+    rows its box kernel wrote; built by hand (xywh=None) they are computed with the reference's torch expressions."""
+
+    def __init__(self, imgs, pred, files, times=None, names=None, shape=None, xywh=None, xyxyn=None, xywhn=None):
+        self.imgs = imgs  # list of images as numpy arrays
+        self.pred = pred  # list of tensors pred[0] = (xyxy, conf, cls)
+        self.names = names
+        self.files = files
+        self.xyxy = pred
+        if xywh is None:
+            gn = [torch.tensor([*(im.shape[i] for i in [1, 0, 1, 0]), 1, 1], device=q.device) for im, q in zip(imgs, pred)]
+            xywh = [xyxy2xywh(x) for x in pred]
+            xyxyn = [x / g for x, g in zip(pred, gn)]
+            xywhn = [x / g for x, g in zip(xywh, gn)]
+        self.xywh, self.xyxyn, self.xywhn = xywh, xyxyn, xywhn
+        self.n = len(self.pred)
+        self.t = tuple((times[i + 1] - times[i]) * 1000 / self.n for i in range(3)) if times is not None else None
+        self.s = shape  # inference BCHW shape
+
+    def _summary(self):
+        """one line per image, as display(pprint=True) logs it (models/common.py:815-837)"""
+        lines = []
+        for i, (im, pred) in enumerate(zip(self.imgs, self.pred)):
+            s = f'image {i + 1}/{len(self.pred)}: {im.shape[0]}x{im.shape[1]} '
+            if pred.shape[0]:
+                for c in pred[:, -1].unique():
+                    k = int((pred[:, -1] == c).sum())
+                    s += f"{k} {self.names[int(c)]}{'s' * (k > 1)}, "
+            else:
+                s += '(no detections)'
+            lines.append(s.rstrip(', '))
+        return lines
+
+    def __str__(self):
+        s = '\n'.join(self._summary())
+        if self.t is not None:
+            s += f'\nSpeed: %.1fms pre-process, %.1fms inference, %.1fms NMS per image at shape {tuple(self.s)}' % self.t
+        return s
+
+    def print(self):
+        for line in str(self).split('\n'):
+            _LOG.info(line)
+
+    def _no_plot(self, *args, **kwargs):
+        raise NotImplementedError('show / save / crop / render need the plotting code (Annotator, save_one_box), '
+                                  'which this project does not have')
+
+    show = save = crop = render = _no_plot
+
+    def pandas(self):
+        """models/common.py:872-880: a copy whose xyxy / xyxyn / xywh / xywhn are lists of pandas DataFrames"""
+        import pandas as pd
+        new = copy(self)
+        ca = 'xmin', 'ymin', 'xmax', 'ymax', 'confidence', 'class', 'name'
+        cb = 'xcenter', 'ycenter', 'width', 'height', 'confidence', 'class', 'name'
+        for k, c in zip(['xyxy', 'xyxyn', 'xywh', 'xywhn'], [ca, ca, cb, cb]):
+            a = [[x[:5] + [int(x[5]), self.names[int(x[5])]] for x in x.tolist()] for x in getattr(self, k)]
+            setattr(new, k, [pd.DataFrame(x, columns=c) for x in a])
+        return new
+
+    def tolist(self):
+        """One Detections per image, its imgs / pred / xyxy / xyxyn / xywh / xywhn popped out of their lists as the
+        reference does (models/common.py:882-888).  Deviation: the reference builds each with
+        Detections([img], [pred], self.names, self.s), which puts `names` in the `files` position and the shape in the
+        `times` position; here every field is the image's own (files = [its file], names, t and s kept)."""
+        res = []
+        for i in range(self.n):
+            d = copy(self)
+            for k in ('imgs', 'pred', 'xyxy', 'xyxyn', 'xywh', 'xywhn'):
+                setattr(d, k, getattr(self, k)[i])
+            d.files, d.n = [self.files[i]], 1
+            res.append(d)
+        return res
+
+    def __len__(self):
+        return self.n

@@ -23,7 +23,7 @@ from .common import *  # noqa: F401,F403  (the YAML namespace)
 from .common import Conv, Upsample, SCConv, GhostConv, GhostBottleneck, autopad, space_to_depth, MP, DMConv, DMMConv, DMMConv2, GnConv
 from .tdetect import TDetect
 from ..utils.general import make_divisible
-from ..utils.torch_utils import initialize_weights, fuse_conv_and_bn
+from ..utils.torch_utils import initialize_weights, fuse_conv_and_bn, copy_attr
 
 _CAT_PLAN = os.environ.get('DMY_CAT_PLAN', '1') == '1'  # see Model._make_cat_plan
 _MODEL_SINKS = os.environ.get('DMY_MODEL_SINKS', '1') != '0'  # Model-level gradient fan-out sinks
@@ -488,6 +488,13 @@ class Model(nn.Module):
             m.anchors = fn(m.anchors)
             m.strides = fn(m.strides)
         return self
+
+    def autoshape(self):
+        """models/yolo.py:325-329: wrap the model for raw-image inference (pre-process, forward, NMS, box rescale)."""
+        from .common import AutoShape
+        m = AutoShape(self)
+        copy_attr(m, self, include=('yaml', 'nc', 'hyp', 'names', 'stride'), exclude=())
+        return m
 
     def info(self, verbose=False, img_size=640):
         n_p = sum(x.numel() for x in self.parameters())

@@ -194,13 +194,21 @@ def non_max_suppression(prediction, conf_thres=0.25, iou_thres=0.45, classes=Non
     batch overflows it (its true count comes back in the same read) the call reruns once at the exact capacity, so
     the top-`max_nms` cut always sees every candidate (utils/general.py:702-703).
     """
+    return nms_padded(prediction, conf_thres, iou_thres, classes, agnostic, multi_label, labels, max_det)[1]
+
+
+def nms_padded(prediction, conf_thres=0.25, iou_thres=0.45, classes=None, agnostic=False, multi_label=False,
+               labels=(), max_det=300):
+    """non_max_suppression that also hands back the buffer its result lives in: (out, res) -- out the
+    (nimg, max_det, 6) device buffer (None for an empty batch), res the per-image views out[b, :keep count] that
+    non_max_suppression returns.  A batched post-process (dmy_scale_boxes) works on `out` with one launch."""
     pred, plan = nms_prepare(prediction, conf_thres, iou_thres, classes, agnostic, multi_label, labels, max_det)
     if pred.shape[0] == 0:
-        return []
+        return None, []
     cap = plan['cap']
     while True:
         cnt, out = nms_launch(pred, plan, cap)
         res = nms_finish(plan, cap, cnt, out)
         if res is not None:
-            return res
+            return out, res
         cap = _CAP_HINT[plan['key']]

@@ -1,6 +1,7 @@
 """utils/torch_utils.py counterparts used on the hot path (initialize_weights, fuse_conv_and_bn,
 ModelEMA, DDP helpers)."""
 import math
+import time
 from copy import deepcopy
 
 import torch
@@ -16,6 +17,21 @@ def is_parallel(model):
 
 def de_parallel(model):
     return model.module if is_parallel(model) else model
+
+
+def time_sync():
+    """utils/torch_utils.py:86-90: a host timestamp after the device has drained."""
+    if torch.cuda.is_available():
+        torch.cuda.synchronize()
+    return time.time()
+
+
+def copy_attr(a, b, include=(), exclude=()):
+    """utils/torch_utils.py:277-283: copy attributes from b to a, with options to only include [...] and to exclude [...]"""
+    for k, v in b.__dict__.items():
+        if (len(include) and k not in include) or k.startswith('_') or k in exclude:
+            continue
+        setattr(a, k, v)
 
 
 def initialize_weights(model):

@@ -618,6 +618,27 @@ int dmy_augment_batch(const void* descs, int n, void* out, int OH, int OW, void*
 long dmy_mosaic_desc_bytes(void);
 int dmy_mosaic_compose(const void* descs, int n, int S2, void* stream);
 
+/* ---- AutoShape (autoshape.hip).
+ *      dmy_letterbox_batch replaces AutoShape.forward's host pre-processing (models/common.py:775-778:
+ *      letterbox(im, new_shape=shape1, auto=False) per image, stack, BHWC -> BCHW, / 255, cast) and the Model.to_input
+ *      that follows: n device-resident 56-byte LetterboxDesc (source uint8 HWC pointer and size, unpadded size, the
+ *      two [4, dst] int32 INTER_LINEAR tables, top / left pad, channel-swap flag; layout in dmayolo/models/common.py
+ *      LETTERBOX_DESC, sizeof = dmy_letterbox_desc_bytes) -> y, the stem input of the batch in dtype (0 fp32, 1 bf16):
+ *      s2d = 1 [n][OH/2][OW/2][Cs] as dmy_image_s2d, s2d = 0 [n][OH][OW][Cs] as dmy_nchw_to_nhwc; the value is the
+ *      letterboxed uint8 level (114 in the border) times scale.  host_descs is the host copy of descs, read for the
+ *      geometry checks: odd OH / OW with s2d, a rectangle outside the canvas, Cs not a whole number of 16-byte vectors
+ *      or y unaligned return hipErrorInvalidValue before any launch.
+ *      dmy_scale_boxes replaces scale_coords (utils/general.py:605-617) per image and the Detections conversions
+ *      (models/common.py:805-808) for the padded NMS output det [nimg][max_det][6] and its int32 keep counts: per
+ *      image geom = (gain, pad_x, pad_y, w0, h0) fp32; det's xyxy is rewritten in place ((x - pad) / gain clamped to
+ *      the image), xywh / xyxyn / xywhn receive xyxy2xywh and the divisions by (w0, h0, w0, h0); rows at or past an
+ *      image's count are not touched.  fp32, IEEE divisions, the reference's operation order. */
+long dmy_letterbox_desc_bytes(void);
+int dmy_letterbox_batch(int dtype, const void* descs, const void* host_descs, int n, void* y, int OH, int OW, int s2d,
+                        int Cs, float scale, void* stream);
+int dmy_scale_boxes(void* det, const void* counts, const void* geom, void* xywh, void* xyxyn, void* xywhn, int nimg,
+                    int max_det, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
