@@ -25,7 +25,7 @@
 // weight-grad accumulators fit the registers, with the dx channels split over 2 blocks per tile where one block's would
 // not), 16-B aligned pixel strides; the host query dmy_conv1x1_bwd_bn_ok says which, everything else keeps the
 // three-pass path.
-#include "common.h"
+#include "launch.h"
 
 namespace {
 namespace b1 {
@@ -381,9 +381,7 @@ int launch(const bf16* dy, long dps, const bf16* z, const bf16* x, long xps, con
 DMY_API int dmy_conv1x1_bwd_bn_ok(long M, int K, int C, long dps, long xps, long bps, const void* dy, const void* z,
                                   const void* x, const void* dx) {
   if (b1::plan(K, C).cb == 0 || M <= 0) return 0;
-  if (dps % 8 || xps % 8 || bps % 8 || dps < K || xps < C || bps < C) return 0;
-  for (const void* p : {dy, z, x, dx})
-    if (((uintptr_t)p & 15) != 0) return 0;
+  if (!vec_ok(8, 0, {dps, xps, bps}, {}, {dy, z, x, dx}) || dps < K || xps < C || bps < C) return 0;
   // 32-bit buffer offsets (the out-of-range offset kOob must stay past every record)
   const double lim = (double)b1::kOob - 64.0;
   if (2.0 * (double)M * dps >= lim || 2.0 * (double)M * K >= lim || 2.0 * (double)M * xps >= lim) return 0;

@@ -19,7 +19,7 @@
 // MFMA: bf16 -> v_mfma_f32_16x16x32_bf16, f32 -> v_mfma_f32_16x16x4_f32 (exact fp32, parity mode).
 // Block ids are remapped so consecutive tiles sharing an A panel land on one XCD (L2 reuse).
 #include <mutex>
-#include "common.h"
+#include "launch.h"
 #include <cstdlib>
 #include <type_traits>
 #include <atomic>
@@ -3457,13 +3457,28 @@ __global__ void __launch_bounds__(256, 1) conv3_halo64(const bf16* __restrict__ 
 }  // namespace v3
 
 // ---------------------------------------------------------------- host dispatch
-Geom make_geom(int N, int H, int W, int C, long xps, int K, int KH, int KW, int S, int P, int OH, int OW, long yps) {
+#define DMY_WGRAD_OIHW 1
+#define DMY_WGRAD_ZEROED 2
+// flags: the weight-grad's DMY_WGRAD_* bits (output layout, caller-cleared output)
+Geom make_geom(int N, int H, int W, int C, long xps, int K, int KH, int KW, int S, int P, int OH, int OW, long yps,
+               int flags = 0) {
   Geom g;
   g.N = N; g.H = H; g.W = W; g.C = C; g.K = K; g.KH = KH; g.KW = KW; g.S = S; g.P = P;
   g.OH = OH; g.OW = OW; g.xps = xps; g.yps = yps;
-  g.oihw = 0; g.zeroed = 0;
+  g.oihw = flags & DMY_WGRAD_OIHW ? 1 : 0;
+  g.zeroed = flags & DMY_WGRAD_ZEROED ? 1 : 0;
   g.dws = nullptr; g.dws_slab = 0;
   return g;
+}
+inline int num_cus() {
+  static int n = [] {
+    int dev = 0, v = 0;
+    if (hipGetDevice(&dev) != hipSuccess ||
+        hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || v <= 0)
+      v = 256;
+    return v;
+  }();
+  return n;
 }
 
 // dw[i] += sum over splits s = 0, 1, ... of ws[s][i], in that order (the deterministic split-K reduction)
@@ -3475,7 +3490,7 @@ __global__ void wgrad_split_reduce(const float* __restrict__ ws, float* __restri
   }
 }
 
-inline bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
+template <int N> using Int = std::integral_constant<int, N>;  // a tile size as a lambda argument
 inline bool is_p1(const Geom& g) { return g.KH == 1 && g.KW == 1 && g.S == 1 && g.P == 0; }
 // byte extents of the bf16 operands of g (H x W x C gather tensor, OH x OW x K output, K x KH x KW x C weights): the
 // num_records of their buffer descriptors, which must stay below the out-of-range offset v3::kBufOob
@@ -3547,58 +3562,47 @@ inline bool big_tile_rows(long M, int N) { return M >= 4096 && N > 64; }
 inline bool big_tile(long M, int N) { return big_tile_rows(M, N) && ceil_div(M, 128) * ceil_div(N, 128) >= 256; }
 
 template <typename T, int BM, int BN>
-int launch_fwd(const T* x, const T* w, const float* b, T* y, float* ps, float* pq, const Geom& g, hipStream_t st,
-               const Epi& ep = Epi{}) {
-  constexpr int VW = Traits<T>::VW;
+int launch_fwd(const void* x, const void* w, const float* b, void* y, float* ps, float* pq, const Geom& g,
+               hipStream_t st, const Epi& ep = Epi{}) {
   const long M = (long)g.N * g.OH * g.OW;
   const int gm = ceil_div(M, BM), gn = ceil_div(g.K, BN);
-  const bool p1 = is_p1(g);
-  const bool vec = g.C % VW == 0 && g.xps % VW == 0 && aligned16(x);
-  const unsigned grid = (unsigned)gm * gn;
-  if (vec && p1) conv_fwd_kernel<T, BM, BN, true, true><<<grid, NT, 0, st>>>(x, w, b, y, ps, pq, g, gm, gn, ep);
-  else if (vec) conv_fwd_kernel<T, BM, BN, true, false><<<grid, NT, 0, st>>>(x, w, b, y, ps, pq, g, gm, gn, ep);
-  else if (p1) conv_fwd_kernel<T, BM, BN, false, true><<<grid, NT, 0, st>>>(x, w, b, y, ps, pq, g, gm, gn, ep);
-  else conv_fwd_kernel<T, BM, BN, false, false><<<grid, NT, 0, st>>>(x, w, b, y, ps, pq, g, gm, gn, ep);
-  return (int)hipGetLastError();
+  const bool vec = vec_ok(Traits<T>::VW, g.C, {g.xps}, {}, {x});
+  return by_flags(vec, is_p1(g), [&](auto VEC, auto P1) {
+    return launch(conv_fwd_kernel<T, BM, BN, VEC.value, P1.value>, (unsigned)gm * gn, NT, 0, st, x, w, b, y, ps, pq, g,
+                  gm, gn, ep);
+  });
 }
 
+// stride 2: the four parity classes along grid.y, no 1x1 form
 template <typename T, int BM, int BN>
-int launch_dgrad(const T* dy, const T* wt, T* dx, int acc, const Geom& g, hipStream_t st) {
-  constexpr int VW = Traits<T>::VW;
-  const bool p1 = is_p1(g);
+int launch_dgrad(const void* dy, const void* wt, void* dx, int acc, const Geom& g, hipStream_t st) {
   const bool s2 = g.S == 2;
   const long M = s2 ? (long)g.N * ((g.H + 1) / 2) * ((g.W + 1) / 2) : (long)g.N * g.H * g.W;
   const int gm = ceil_div(M, BM), gn = ceil_div(g.C, BN);
-  const bool vec = g.K % VW == 0 && g.yps % VW == 0 && aligned16(dy);
-  const dim3 grid((unsigned)gm * gn, s2 ? 4 : 1);
-  if (s2) {
-    if (vec) conv_dgrad_kernel<T, BM, BN, true, false, true><<<grid, NT, 0, st>>>(dy, wt, dx, acc, g, gm, gn);
-    else conv_dgrad_kernel<T, BM, BN, false, false, true><<<grid, NT, 0, st>>>(dy, wt, dx, acc, g, gm, gn);
-  } else if (vec && p1) conv_dgrad_kernel<T, BM, BN, true, true, false><<<grid, NT, 0, st>>>(dy, wt, dx, acc, g, gm, gn);
-  else if (vec) conv_dgrad_kernel<T, BM, BN, true, false, false><<<grid, NT, 0, st>>>(dy, wt, dx, acc, g, gm, gn);
-  else if (p1) conv_dgrad_kernel<T, BM, BN, false, true, false><<<grid, NT, 0, st>>>(dy, wt, dx, acc, g, gm, gn);
-  else conv_dgrad_kernel<T, BM, BN, false, false, false><<<grid, NT, 0, st>>>(dy, wt, dx, acc, g, gm, gn);
-  return (int)hipGetLastError();
+  const bool vec = vec_ok(Traits<T>::VW, g.K, {g.yps}, {}, {dy});
+  auto go = [&](auto VEC, auto P1, auto S2) {
+    return launch(conv_dgrad_kernel<T, BM, BN, VEC.value, P1.value, S2.value>, dim3((unsigned)gm * gn, s2 ? 4 : 1), NT,
+                  0, st, dy, wt, dx, acc, g, gm, gn);
+  };
+  if (s2) return by_flags(vec, [&](auto VEC) { return go(VEC, std::false_type{}, std::true_type{}); });
+  return by_flags(vec, is_p1(g), [&](auto VEC, auto P1) { return go(VEC, P1, std::false_type{}); });
 }
 
 template <typename T, int BM, int BN>
-void launch_wgrad(const T* x, const T* dy, float* dw, const Geom& g, hipStream_t st, const WPlan& pl) {
+int launch_wgrad(const void* x, const void* dy, float* dw, const Geom& g, hipStream_t st, const WPlan& pl) {
   constexpr int VW = Traits<T>::VW;
-  const int Ntot = g.KH * g.KW * g.C;
-  const int gm = ceil_div(g.K, BM), gn = ceil_div(Ntot, BN);
-  const dim3 grid((unsigned)gm * gn, pl.splits);
-  const bool va = g.K % VW == 0 && g.yps % VW == 0 && aligned16(dy);
-  const bool vb = g.C % VW == 0 && g.xps % VW == 0 && aligned16(x);
-  if (va && vb) conv_wgrad_kernel<T, BM, BN, true, true><<<grid, NT, 0, st>>>(x, dy, dw, pl.per, g, gm, gn);
-  else if (va) conv_wgrad_kernel<T, BM, BN, true, false><<<grid, NT, 0, st>>>(x, dy, dw, pl.per, g, gm, gn);
-  else if (vb) conv_wgrad_kernel<T, BM, BN, false, true><<<grid, NT, 0, st>>>(x, dy, dw, pl.per, g, gm, gn);
-  else conv_wgrad_kernel<T, BM, BN, false, false><<<grid, NT, 0, st>>>(x, dy, dw, pl.per, g, gm, gn);
+  const int gm = ceil_div(g.K, BM), gn = ceil_div(g.KH * g.KW * g.C, BN);
+  return by_flags(vec_ok(VW, g.K, {g.yps}, {}, {dy}), vec_ok(VW, g.C, {g.xps}, {}, {x}), [&](auto VA, auto VB) {
+    return launch(conv_wgrad_kernel<T, BM, BN, VA.value, VB.value>, dim3((unsigned)gm * gn, pl.splits), NT, 0, st, x,
+                  dy, dw, pl.per, g, gm, gn);
+  });
 }
 
+// the inference epilogue's residual is absent or read as 16-B vectors (its channel count is the output's, tested there)
+inline bool res_ok(const void* res, long rps) { return res == nullptr || vec_ok(8, 0, {rps}, {res}); }
 // v3 (LDS-DMA) kernels apply to bf16 with 16-B vectors everywhere and enough rows to fill the chip
 inline bool v3_ok(int C, long xps, int K, long yps, const void* x, const void* w, const void* y, long M) {
-  return C % 8 == 0 && xps % 8 == 0 && K % 8 == 0 && yps % 8 == 0 && aligned16(x) && aligned16(w) && aligned16(y) &&
-         M >= 16384 && K >= 32;
+  return vec_ok(8, C, {xps, K, yps}, {}, {x, w, y}) && M >= 16384 && K >= 32;
 }
 
 // gv = GEMM view (rows N*OH*OW, columns K, gather tensor H x W x C with stride xps); BN partials need
@@ -3612,7 +3616,6 @@ inline bool v3_ok(int C, long xps, int K, long yps, const void* x, const void* w
 // the half-tile pipeline on 3x3 tiles (gpurun_out/r5/ab_w8p.log), the streaming GEMM's 1x1 eval epilogue
 // (profiles/r04/det_p1s_ep_ab.log) and the fragments-first orders of the halo / tap / persistent 1x1 loops
 // (profiles/r04/halo_tap_ff_ab.log, p1p_ff_ab.log).  What is left has one path per shape class.
-inline int num_cus();
 // wide 256 x 256 tiles (v3::conv_fwd_w) for GEMM views with >= 256 columns and at least one block per CU: +9..21 % on
 // every DMA-YOLO / yolov5s shape with >= 256 columns, 0.66-0.76x at 128 columns or below one block per CU
 // (profiles/r02/ab_wide.log).  The 1x1 views among them run the half-tile pipeline (v3::conv_fwd_8p; round 5,
@@ -3637,8 +3640,7 @@ inline int wide_rows(long M, long gn) {
 inline bool p1s_ok(const Geom& gv, const void* x, const void* w, const void* y) {
   if (!is_p1(gv)) return false;
   if (gv.C != 64 && gv.C != 128 && gv.C != 256) return false;
-  if (gv.K % 32 != 0 || gv.xps % 8 != 0 || gv.yps % 8 != 0 || !aligned16(x) || !aligned16(w) || !aligned16(y))
-    return false;
+  if (gv.K % 32 != 0 || !vec_ok(8, gv.C, {gv.xps, gv.yps}, {}, {x, w, y})) return false;
   return fits_buf(2.0 * ((double)gv.N * gv.OH * gv.OW * gv.xps));
 }
 // threads per block of the training stem: 512 = 64-column passes that write whole 128-B output lines per pixel, for
@@ -3649,8 +3651,7 @@ inline int stem_nth(int K) { return K >= 64 ? 512 : 768; }
 // the k3 s1 p1 view of the space-to-depth stem (16 input channels) on the streaming GEMM with its 3x3 gather
 inline bool stem_s_ok(const Geom& gv, const void* x, const void* w, const void* y) {
   if (gv.C != 16 || gv.KH != 3 || gv.KW != 3 || gv.S != 1 || gv.P != 1 || gv.OH != gv.H || gv.OW != gv.W) return false;
-  if (gv.K % 32 != 0 || gv.K > 256 || gv.xps % 8 != 0 || gv.yps % 8 != 0 || !aligned16(x) || !aligned16(w) || !aligned16(y))
-    return false;
+  if (gv.K % 32 != 0 || gv.K > 256 || !vec_ok(8, gv.C, {gv.xps, gv.yps}, {}, {x, w, y})) return false;
   return fits_buf(x_bytes(gv)) && (long)gv.N * gv.H * gv.W < (1L << 31);
 }
 // column groups of a streaming-GEMM launch (conv_p1s, 512 threads, 160 KiB of LDS): each group holds ng columns of W
@@ -3660,7 +3661,7 @@ inline int p1s_groups(int KD, int NC) {
   return ceil_div(NC, ng);
 }
 template <int KD, int NTH, bool G3 = false, bool DG = false>
-int launch_p1s_kd(const bf16* x, const bf16* w, const float* b, bf16* y, float* ps, float* pq, int acc,
+int launch_p1s_kd(const void* x, const void* w, const float* b, void* y, float* ps, float* pq, int acc,
                   const Geom& gv, hipStream_t st, int lds_kib, int bpc) {
   constexpr int pitch_b = (KD + 8) * 2, scratch = NTH / 64 * 256;
   const long M = (long)gv.N * gv.OH * gv.OW;
@@ -3680,14 +3681,12 @@ int launch_p1s_kd(const bf16* x, const bf16* w, const float* b, bf16* y, float* 
   const int maxb = ceil_div(ntiles, NTH / 64);
   if (nbx > maxb) nbx = maxb;
   const dim3 grid((unsigned)nbx, (unsigned)G);
-  const double xb = x_bytes(gv);
-  v3::conv_p1s<KD, NTH, G3, DG><<<grid, NTH, lds, st>>>(x, w, b, y, ps, pq, acc, M, gv.K, ng, gv.xps, gv.yps, (unsigned)xb,
-                                               ntiles, gv.KH * gv.KW * gv.C, gv.H, gv.W);
-  return (int)hipGetLastError();
+  return launch(v3::conv_p1s<KD, NTH, G3, DG>, grid, NTH, lds, st, x, w, b, y, ps, pq, acc, M, gv.K, ng, gv.xps, gv.yps,
+                (unsigned)x_bytes(gv), ntiles, gv.KH * gv.KW * gv.C, gv.H, gv.W);
 }
 // training forwards: 512 threads, the whole 160 KiB of LDS for the W column group, one block per CU
 template <bool DG = false>
-inline int launch_p1s(const bf16* x, const bf16* w, const float* b, bf16* y, float* ps, float* pq, int acc,
+inline int launch_p1s(const void* x, const void* w, const float* b, void* y, float* ps, float* pq, int acc,
                       const Geom& gv, hipStream_t st) {
   if (gv.C == 64) return launch_p1s_kd<64, 512, false, DG>(x, w, b, y, ps, pq, acc, gv, st, 160, 1);
   if (gv.C == 128) return launch_p1s_kd<128, 512, false, DG>(x, w, b, y, ps, pq, acc, gv, st, 160, 1);
@@ -3720,22 +3719,16 @@ int p1p_plan(const Geom& gv, int acc, const Epi& ep, F&& f) {
   const int nk = gv.C / v3::BK;
   const double yb = 2.0 * ((double)(M - 1) * gv.yps + gv.K);
   const double rb = ep.res != nullptr ? 2.0 * ((double)(M - 1) * ep.rps + gv.K) : 0.0;
-  if (acc || gv.K % 8 != 0 || !fits_buf(yb) || !fits_buf(rb) || nk < 1 ||
-      (ep.res != nullptr && (ep.rps % 8 != 0 || !aligned16(ep.res))) || gv.K > kP1pMaxCols)
+  if (acc || gv.K % 8 != 0 || !fits_buf(yb) || !fits_buf(rb) || nk < 1 || !res_ok(ep.res, ep.rps) ||
+      gv.K > kP1pMaxCols)
     return -1;
   // 129..256 columns over a >= 1024-deep reduction: the 256 x 256 half-tile pipeline reads each input row once and
   // keeps its 16+ K steps in flight (profiles/r06/route_ab.log, cold caches: 1024 -> 256 @96^2 fwd 224 -> 201 us,
   // 1280 -> 256 fwd 288 -> 245, data-grad 256 <- 1024 208 -> 184; the 256-deep 256 -> 256 stays here, 86 vs 102 us)
   if (gv.K > 128 && gv.C >= 1024) return -1;
-  using std::integral_constant;
-#define P1P_CFG(BM, BN, NS, WTR) \
-  return f(integral_constant<int, BM>{}, integral_constant<int, BN>{}, integral_constant<int, NS>{}, integral_constant<int, WTR>{})
-  if (gv.K > 64) {
-    if (nk >= 2) P1P_CFG(256, 128, 3, 64);
-    P1P_CFG(256, 128, 2, 64);
-  }
-  P1P_CFG(256, 64, 2, 64);
-#undef P1P_CFG
+  if (gv.K > 64 && nk >= 2) return f(Int<256>{}, Int<128>{}, Int<3>{}, Int<64>{});
+  if (gv.K > 64) return f(Int<256>{}, Int<128>{}, Int<2>{}, Int<64>{});
+  return f(Int<256>{}, Int<64>{}, Int<2>{}, Int<64>{});
 }
 // BN partial rows of a LANE launch (one per wave row of the persistent grid), or 0 when launch_p1p would not use LANE
 inline long p1p_lane_rows(const Geom& gv) {
@@ -3748,7 +3741,7 @@ inline long p1p_lane_rows(const Geom& gv) {
   });
 }
 template <bool DG>
-int launch_p1p(const bf16* x, const bf16* w, const float* b, bf16* y, float* ps, float* pq, int acc, const Geom& gv,
+int launch_p1p(const void* x, const void* w, const float* b, void* y, float* ps, float* pq, int acc, const Geom& gv,
                hipStream_t st, unsigned xbytes, unsigned wbytes, const Epi& ep, bool lane) {
   const long M = (long)gv.N * gv.OH * gv.OW;
   const double yb = 2.0 * ((double)(M - 1) * gv.yps + gv.K);
@@ -3758,17 +3751,14 @@ int launch_p1p(const bf16* x, const bf16* w, const float* b, bf16* y, float* ps,
     using PP = v3::P1P<BM, BN, NS, WTR>;
     const int gm = ceil_div(M, BM), gn = ceil_div(gv.K, BN), ntiles = gm * gn;
     const int G = p1p_grid(ntiles, PP::LDS);
-    if constexpr (!DG) {
-      if (lane) {  // one BN partial row per wave (plan_v3: p1p_lane_rows)
-        v3::conv_p1p<BM, BN, NS, WTR, false, true><<<(unsigned)G, PP::NTH, 0, st>>>(
-            x, w, b, y, ps, pq, acc, gv, gm, gn, xbytes, wbytes, (unsigned)yb, G * PP::C3_::WM, ep, (unsigned)rb);
-        return (int)hipGetLastError();
-      }
-    }
-    const int nprow = ps != nullptr ? dmy_conv_fwd_partial_rows(M, gv.K) : 0;
-    v3::conv_p1p<BM, BN, NS, WTR, DG><<<(unsigned)G, PP::NTH, 0, st>>>(x, w, b, y, ps, pq, acc, gv, gm, gn, xbytes,
-                                                                      wbytes, (unsigned)yb, nprow, ep, (unsigned)rb);
-    return (int)hipGetLastError();
+    // LANE (forward only): one BN partial row per wave (plan_v3: p1p_lane_rows)
+    const int nprow = !DG && lane ? G * PP::C3_::WM : ps != nullptr ? dmy_conv_fwd_partial_rows(M, gv.K) : 0;
+    auto go = [&](auto LANE) {
+      return launch(v3::conv_p1p<BM, BN, NS, WTR, DG, LANE.value>, (unsigned)G, PP::NTH, 0, st, x, w, b, y, ps, pq, acc,
+                    gv, gm, gn, xbytes, wbytes, (unsigned)yb, nprow, ep, (unsigned)rb);
+    };
+    if constexpr (DG) return go(std::false_type{});
+    else return by_flags(lane, go);
   });
 }
 
@@ -3778,8 +3768,8 @@ int launch_p1p(const bf16* x, const bf16* w, const float* b, bf16* y, float* ps,
 inline long halo_units(const Geom& g) { return (long)g.N * (g.H / v3::halo::TH) * (g.W / v3::halo::TW); }
 inline bool halo_ok(const Geom& g, const void* x, const void* w, const void* y) {
   if (g.KH != 3 || g.KW != 3 || g.S != 1 || g.P != 1 || g.C != 64 || g.K != 64 ||
-      g.OH != g.H || g.OW != g.W || g.H % v3::halo::TH != 0 || g.W % v3::halo::TW != 0 || g.xps % 8 != 0 ||
-      g.yps % 8 != 0 || !aligned16(x) || !aligned16(w) || !aligned16(y))
+      g.OH != g.H || g.OW != g.W || g.H % v3::halo::TH != 0 || g.W % v3::halo::TW != 0 ||
+      !vec_ok(8, g.C, {g.xps, g.yps}, {}, {x, w, y}))
     return false;
   return fits_buf(x_bytes(g)) && fits_buf(y_bytes(g)) && halo_units(g) >= num_cus();
 }
@@ -3793,20 +3783,18 @@ inline int halo_blocks(const Geom& g, int* per_out = nullptr) {
 // BN partial rows the halo kernel writes: one per wave
 inline int halo_rows(const Geom& g) { return v3::halo::NW * halo_blocks(g); }
 template <bool DG>
-int launch_halo(const bf16* x, const bf16* w, bf16* y, float* ps, float* pq, const Geom& g, hipStream_t st,
+int launch_halo(const void* x, const void* w, void* y, float* ps, float* pq, const Geom& g, hipStream_t st,
                 int acc = 0, const Epi& ep = Epi{}) {
   const int thn = g.H / v3::halo::TH, twn = g.W / v3::halo::TW, nt = (int)halo_units(g);
   int per = 1;
   const int G = halo_blocks(g, &per);
   const unsigned xb = (unsigned)x_bytes(g), yb = (unsigned)y_bytes(g);
   const unsigned rb = ep.res != nullptr ? (unsigned)(2.0 * ((double)g.N * g.OH * g.OW * ep.rps)) : 0u;
-  if (!DG && ep.on)  // inference epilogue: its own instantiation, so the training kernel's registers are untouched
-    v3::conv3_halo64<false, true><<<(unsigned)G, 64 * v3::halo::NW, 0, st>>>(x, w, y, ps, pq, g, twn, thn, nt, per,
-                                                                           xb, 2u * 64 * 576, yb, acc, ep, rb);
-  else
-    v3::conv3_halo64<DG><<<(unsigned)G, 64 * v3::halo::NW, 0, st>>>(x, w, y, ps, pq, g, twn, thn, nt, per, xb,
-                                                                    2u * 64 * 576, yb, acc, ep, rb);
-  return (int)hipGetLastError();
+  // a forward's inference epilogue: its own instantiation, so the training kernel's registers are untouched
+  return by_flags(!DG && ep.on, [&](auto EP) {
+    return launch(v3::conv3_halo64<DG && !EP.value, EP.value>, (unsigned)G, 64 * v3::halo::NW, 0, st, x, w, y, ps, pq, g,
+                  twn, thn, nt, per, xb, 2u * 64 * 576, yb, acc, ep, rb);
+  });
 }
 
 // the v3 family for GEMM view gv (forward, or data-grad when DG)
@@ -3852,31 +3840,28 @@ Plan plan_v3(const Geom& gv, const void* x, const void* w, const void* y, int ac
   return pl;
 }
 template <bool DG>
-int launch_v3(const bf16* x, const bf16* w, const float* b, bf16* y, float* ps, float* pq, int acc, const Geom& gv,
+int launch_v3(const void* x, const void* w, const float* b, void* y, float* ps, float* pq, int acc, const Geom& gv,
               hipStream_t st, const Epi& ep, const Plan& pl) {
   const long M = (long)gv.N * gv.OH * gv.OW;
   const bool p1 = is_p1(gv);
   const unsigned xbytes = pl.buf ? (unsigned)x_bytes(gv) : 0u, wbytes = pl.buf ? (unsigned)w_bytes(gv) : 0u;
-#define W_GO(BM, BN)                                                                                                 \
-  {                                                                                                                  \
-    const int gm = ceil_div(M, BM), gn = ceil_div(gv.K, BN);                                                         \
-    if (p1) v3::conv_fwd_w<BM, BN, true, DG><<<(unsigned)gm * gn, 512, 0, st>>>(x, w, b, y, ps, pq, acc, gv, gm, gn, \
-                                                                              xbytes, wbytes, ep);                  \
-    else v3::conv_fwd_w<BM, BN, false, DG><<<(unsigned)gm * gn, 512, 0, st>>>(x, w, b, y, ps, pq, acc, gv, gm, gn,   \
-                                                                               xbytes, wbytes, ep);                 \
-    return (int)hipGetLastError();                                                                                   \
-  }
-#define V3_GO(BM, BN, NS, BUF_)                                                                               \
-  {                                                                                                           \
-    const int gm = ceil_div(M, BM), gn = ceil_div(gv.K, BN);                                                  \
-    if (p1)                                                                                                   \
-      v3::conv_fwd_v3<BM, BN, NS, true, DG, BUF_><<<(unsigned)gm * gn, BM * BN / 64, 0, st>>>(                \
-          x, w, b, y, ps, pq, acc, gv, gm, gn, xbytes, wbytes, v3::S2Cls{0, 0, 0, 0}, ep);                    \
-    else                                                                                                      \
-      v3::conv_fwd_v3<BM, BN, NS, false, DG, BUF_><<<(unsigned)gm * gn, BM * BN / 64, 0, st>>>(               \
-          x, w, b, y, ps, pq, acc, gv, gm, gn, xbytes, wbytes, v3::S2Cls{0, 0, 0, 0}, ep);                    \
-    return (int)hipGetLastError();                                                                            \
-  }
+  // the wide / tall tiles (conv_fwd_w) and the 4-wave-row LDS-DMA tiles (conv_fwd_v3), each with its 1x1 form
+  auto wide = [&](auto bm, auto bn) {
+    constexpr int BM = decltype(bm)::value, BN = decltype(bn)::value;
+    const int gm = ceil_div(M, BM), gn = ceil_div(gv.K, BN);
+    return by_flags(p1, [&](auto P1) {
+      return launch(v3::conv_fwd_w<BM, BN, P1.value, DG>, (unsigned)gm * gn, 512, 0, st, x, w, b, y, ps, pq, acc, gv,
+                    gm, gn, xbytes, wbytes, ep);
+    });
+  };
+  auto tile = [&](auto bm, auto bn, auto ns) {
+    constexpr int BM = decltype(bm)::value, BN = decltype(bn)::value, NS = decltype(ns)::value;
+    const int gm = ceil_div(M, BM), gn = ceil_div(gv.K, BN);
+    return by_flags(p1, pl.buf, [&](auto P1, auto BUF) {
+      return launch(v3::conv_fwd_v3<BM, BN, NS, P1.value, DG, BUF.value>, (unsigned)gm * gn, BM * BN / 64, 0, st, x, w,
+                    b, y, ps, pq, acc, gv, gm, gn, xbytes, wbytes, v3::S2Cls{0, 0, 0, 0}, ep);
+    });
+  };
   switch (pl.k) {
     case Kern::P1S: return launch_p1s<DG>(x, w, b, y, ps, pq, acc, gv, st);
     case Kern::STEM:
@@ -3885,22 +3870,15 @@ int launch_v3(const bf16* x, const bf16* w, const float* b, bf16* y, float* ps, 
     case Kern::P1P: return launch_p1p<DG>(x, w, b, y, ps, pq, acc, gv, st, xbytes, wbytes, ep, pl.lane);
     case Kern::PIPE8: {
       const int gm = ceil_div(M, 256), gn = ceil_div(gv.K, 256);
-      v3::conv_fwd_8p<true, DG><<<(unsigned)gm * gn, 512, 0, st>>>(x, w, b, y, ps, pq, acc, gv, gm, gn, xbytes, wbytes, ep);
-      return (int)hipGetLastError();
+      return launch(v3::conv_fwd_8p<true, DG>, (unsigned)gm * gn, 512, 0, st, x, w, b, y, ps, pq, acc, gv, gm, gn,
+                    xbytes, wbytes, ep);
     }
-    case Kern::WIDE: W_GO(256, 256)
-    case Kern::WIDE288: W_GO(288, 256)
-    case Kern::TALL: W_GO(512, 128)
+    case Kern::WIDE: return wide(Int<256>{}, Int<256>{});
+    case Kern::WIDE288: return wide(Int<288>{}, Int<256>{});
+    case Kern::TALL: return wide(Int<512>{}, Int<128>{});
     default: break;
   }
-  if (gv.K > 64) {
-    if (pl.buf) V3_GO(256, 128, 3, 1)
-    V3_GO(256, 128, 3, 0)
-  }
-  if (pl.buf) V3_GO(256, 64, 2, 1)
-  V3_GO(256, 64, 2, 0)
-#undef W_GO
-#undef V3_GO
+  return gv.K > 64 ? tile(Int<256>{}, Int<128>{}, Int<3>{}) : tile(Int<256>{}, Int<64>{}, Int<2>{});
 }
 
 // sum the split slabs in order, + bias, round to bf16, inference epilogue (or plain store)
@@ -3933,8 +3911,7 @@ __global__ void __launch_bounds__(256) splitk_epi_kernel(const float* __restrict
 // and the buffer loader applies; 0 = not split
 inline int splitk_plan(const Geom& g, const void* x, const void* w, const void* y, int& gm, int& gn, int& per) {
   const long M = (long)g.N * g.OH * g.OW;
-  if (M >= 16384 || M == 0 || g.C % 64 != 0 || g.xps % 8 != 0 || g.K % 8 != 0 || g.yps % 8 != 0 || g.K < 32 ||
-      !aligned16(x) || !aligned16(w) || !aligned16(y))
+  if (M >= 16384 || M == 0 || g.C % 64 != 0 || g.K < 32 || !vec_ok(8, g.C, {g.xps, g.K, g.yps}, {}, {x, w, y}))
     return 0;
   if (!fits_buf(x_bytes(g)) || !fits_buf(w_bytes(g))) return 0;
   // detect-path A/B (profiles/r02/det_splitk.log): target 2 blocks per CU, at least 2 K steps per split; 1x1 layers
@@ -3959,39 +3936,35 @@ inline long splitk_elems(const Geom& g, const void* x, const void* w, const void
   return sp ? (long)sp * g.N * g.OH * g.OW * g.K : 0;
 }
 
-inline int launch_splitk(const bf16* x, const bf16* w, const float* b, bf16* y, const Geom& g, float* ws, hipStream_t st,
-                         const Epi& ep) {
+inline int launch_splitk(const void* x, const void* w, const float* b, void* y, const Geom& g, float* ws,
+                         hipStream_t st, const Epi& ep) {
   int gm, gn, per;
   const int sp = splitk_plan(g, x, w, y, gm, gn, per);
   const long M = (long)g.N * g.OH * g.OW;
   const unsigned xb = (unsigned)x_bytes(g), wb = (unsigned)w_bytes(g);
-  const bool p1 = is_p1(g);
-  const dim3 grid((unsigned)gm * gn, (unsigned)sp);
-  if (g.K > 64) {
-    if (p1) v3::conv_fwd_split<128, 128, 2, true><<<grid, 256, 0, st>>>(x, w, ws, g, gm, gn, per, xb, wb);
-    else v3::conv_fwd_split<128, 128, 2, false><<<grid, 256, 0, st>>>(x, w, ws, g, gm, gn, per, xb, wb);
-  } else {
-    if (p1) v3::conv_fwd_split<128, 64, 2, true><<<grid, 128, 0, st>>>(x, w, ws, g, gm, gn, per, xb, wb);
-    else v3::conv_fwd_split<128, 64, 2, false><<<grid, 128, 0, st>>>(x, w, ws, g, gm, gn, per, xb, wb);
-  }
-  splitk_epi_kernel<<<grid_cap(ceil_div(M * (g.K / 8), 256), 4096), 256, 0, st>>>(ws, sp, M, g.K, b, y, g.yps, ep);
-  return (int)hipGetLastError();
+  const int rc = by_flags(g.K > 64, is_p1(g), [&](auto BIG, auto P1) {
+    constexpr int BN = BIG.value ? 128 : 64;
+    return launch(v3::conv_fwd_split<128, BN, 2, P1.value>, dim3((unsigned)gm * gn, (unsigned)sp), 128 * BN / 64, 0, st,
+                  x, w, ws, g, gm, gn, per, xb, wb);
+  });
+  if (rc != 0) return rc;
+  return launch(splitk_epi_kernel, grid_cap(ceil_div(M * (g.K / 8), 256), 4096), st, ws, sp, M, g.K, b, y, g.yps, ep);
 }
 
 // the bf16 forward's plan: bn = the launch writes BN partials (training); ws_elems = the split-K workspace it has
 Plan plan_fwd(const Geom& g, const void* x, const void* w, const float* b, const void* y, bool bn, const Epi& ep,
               long ws_elems) {
   const long M = (long)g.N * g.OH * g.OW;
-  const bool res_ok = !ep.res || (ep.rps % 8 == 0 && aligned16(ep.res));
+  const bool rv = res_ok(ep.res, ep.rps);
   if (b == nullptr && halo_ok(g, x, w, y) && (!ep.on || !bn) && halo_rows(g) <= prow_persist_cap() &&
       (!ep.on || ep.res == nullptr ||
-       (res_ok && fits_buf(2.0 * ((double)g.N * g.OH * g.OW * ep.rps)))))
+       (rv && fits_buf(2.0 * ((double)g.N * g.OH * g.OW * ep.rps)))))
     return Plan{Kern::HALO, true, false, halo_rows(g)};  // one BN partial row per wave
-  if (ws_elems > 0 && !bn && res_ok) {
+  if (ws_elems > 0 && !bn && rv) {
     const long need = splitk_elems(g, x, w, y);
     if (need > 0 && need <= ws_elems) return Plan{Kern::SPLITK, true, false, 0};
   }
-  if (v3_ok(g.C, g.xps, g.K, g.yps, x, w, y, M) && res_ok) return plan_v3<false>(g, x, w, y, 0, ep);
+  if (v3_ok(g.C, g.xps, g.K, g.yps, x, w, y, M) && rv) return plan_v3<false>(g, x, w, y, 0, ep);
   return Plan{Kern::V2, false, false, dmy_conv_fwd_partial_rows(M, g.K)};
 }
 
@@ -4004,15 +3977,15 @@ int conv_fwd_t(const void* x, const void* w, const float* b, void* y, float* ps,
   if (ps != nullptr) t_prow_last = pl.rows;
   if constexpr (sizeof(T) == 2) {
     switch (pl.k) {
-      case Kern::HALO: return launch_halo<false>((const bf16*)x, (const bf16*)w, (bf16*)y, ps, pq, g, st, 0, ep);
-      case Kern::SPLITK: return launch_splitk((const bf16*)x, (const bf16*)w, b, (bf16*)y, g, ws, st, ep);
+      case Kern::HALO: return launch_halo<false>(x, w, y, ps, pq, g, st, 0, ep);
+      case Kern::SPLITK: return launch_splitk(x, w, b, y, g, ws, st, ep);
       case Kern::V2: break;
-      default: return launch_v3<false>((const bf16*)x, (const bf16*)w, b, (bf16*)y, ps, pq, 0, g, st, ep, pl);
+      default: return launch_v3<false>(x, w, b, y, ps, pq, 0, g, st, ep, pl);
     }
   }
   if (ps != nullptr ? big_tile_rows(M, g.K) : big_tile(M, g.K))
-    return launch_fwd<T, 128, 128>((const T*)x, (const T*)w, b, (T*)y, ps, pq, g, st, ep);
-  return launch_fwd<T, 64, 64>((const T*)x, (const T*)w, b, (T*)y, ps, pq, g, st, ep);
+    return launch_fwd<T, 128, 128>(x, w, b, y, ps, pq, g, st, ep);
+  return launch_fwd<T, 64, 64>(x, w, b, y, ps, pq, g, st, ep);
 }
 // ---------------------------------------------------------------- data-grad
 // stride-1 data-grad as a forward over its GEMM view: rows = input pixels (N, H, W), columns = C, gather dy
@@ -4062,25 +4035,24 @@ Plan plan_dgrad(const Geom& g, const void* dy, const void* wt, const void* dx, i
 // stride-2 data-grad on the v3 buffer loader (plan_dgrad's S2_* kinds): one GEMM over dy pixels, the four output-parity
 // classes (a, b) in one launch, or one launch per class, each a GEMM over the class's input pixels and only the taps
 // of matching parity (FwdLdsB S2 mode)
-inline int launch_dgrad_s2(const bf16* dy, const bf16* wt, bf16* dx, int acc, const Geom& g, hipStream_t st, Kern k) {
+inline int launch_dgrad_s2(const void* dy, const void* wt, void* dx, int acc, const Geom& g, hipStream_t st, Kern k) {
   const unsigned xbytes = (unsigned)y_bytes(g), wbytes = (unsigned)w_bytes(g);
   if (k == Kern::S2_Q2S || k == Kern::S2_Q2) {
     const int gm = (int)ceil_div((long)g.N * g.OH * g.OW, 256);
     // GEMM view: rows = dy pixels, the 2 x 2 dy window as taps, columns = classes x channels
     const Geom gq = make_geom(g.N, g.OH, g.OW, g.K, g.yps, g.C == 32 ? 128 : 256, 2, 2, 1, 0, g.OH, g.OW, g.xps);
     const v3::S2Cls c0{0, 0, g.H, g.W};
-    if (g.C == 32) v3::conv_dgrad_q2s<<<(unsigned)gm, 512, 0, st>>>(dy, wt, dx, acc, gq, gm, xbytes, wbytes, c0);
-    else if (g.C == 64) v3::conv_dgrad_q2<64><<<(unsigned)gm, 512, 0, st>>>(dy, wt, dx, acc, gq, gm, xbytes, wbytes, c0);
-    else v3::conv_dgrad_q2<128><<<(unsigned)(2 * gm), 512, 0, st>>>(dy, wt, dx, acc, gq, gm, xbytes, wbytes, c0);
-    return (int)hipGetLastError();
+    if (g.C == 32) return launch(v3::conv_dgrad_q2s, gm, 512, 0, st, dy, wt, dx, acc, gq, gm, xbytes, wbytes, c0);
+    if (g.C == 64) return launch(v3::conv_dgrad_q2<64>, gm, 512, 0, st, dy, wt, dx, acc, gq, gm, xbytes, wbytes, c0);
+    return launch(v3::conv_dgrad_q2<128>, 2 * gm, 512, 0, st, dy, wt, dx, acc, gq, gm, xbytes, wbytes, c0);
   }
   if (k == Kern::S2_MERGED) {
     const long Mmax = (long)g.N * ((g.H + 1) / 2) * ((g.W + 1) / 2);  // class (0, 0) has the most rows
     const int gmax = ceil_div(Mmax, 256), gn = ceil_div(g.C, 64);
-    v3::conv_dgrad_s2_v3<256, 64, 2><<<(unsigned)(4 * gmax * gn), 256, 0, st>>>(dy, wt, dx, acc, g, gmax, gn, xbytes,
-                                                                              wbytes);
-    return (int)hipGetLastError();
+    return launch(v3::conv_dgrad_s2_v3<256, 64, 2>, 4 * gmax * gn, 256, 0, st, dy, wt, dx, acc, g, gmax, gn, xbytes,
+                  wbytes);
   }
+  int rc = 0;
   for (int a = 0; a < 2; ++a)
     for (int b = 0; b < 2; ++b) {
       const int H2 = (g.H - a + 1) / 2, W2 = (g.W - b + 1) / 2;
@@ -4095,22 +4067,20 @@ inline int launch_dgrad_s2(const bf16* dy, const bf16* wt, bf16* dx, int acc, co
       // measured 1228 -> 1257 and is not used)
       if (g.C % 256 == 0 && (long)ceil_div(M, 256) * (g.C / 256) >= num_cus()) {
         const int gn = g.C / 256;
-        if (wide_rows(M, gn) == 288) {
-          const int gm = ceil_div(M, 288);
-          v3::conv_dgrad_s2_w<288, 256><<<(unsigned)gm * gn, 512, 0, st>>>(dy, wt, dx, acc, gv, gm, gn, xbytes, wbytes,
-                                                                            cls);
-        } else {
-          const int gm = ceil_div(M, 256);
-          v3::conv_dgrad_s2_w<256, 256><<<(unsigned)gm * gn, 512, 0, st>>>(dy, wt, dx, acc, gv, gm, gn, xbytes, wbytes,
-                                                                            cls);
-        }
+        rc = by_flags(wide_rows(M, gn) == 288, [&](auto R288) {
+          constexpr int BM = R288.value ? 288 : 256;
+          const int gm = ceil_div(M, BM);
+          return launch(v3::conv_dgrad_s2_w<BM, 256>, (unsigned)gm * gn, 512, 0, st, dy, wt, dx, acc, gv, gm, gn, xbytes,
+                        wbytes, cls);
+        });
       } else {
         const int gm = ceil_div(M, 256), gn = ceil_div(g.C, 128);
-        v3::conv_fwd_v3<256, 128, 3, false, true, 3><<<(unsigned)gm * gn, 512, 0, st>>>(
-            dy, wt, nullptr, dx, nullptr, nullptr, acc, gv, gm, gn, xbytes, wbytes, cls, Epi{});
+        rc = launch(v3::conv_fwd_v3<256, 128, 3, false, true, 3>, (unsigned)gm * gn, 512, 0, st, dy, wt, nullptr, dx,
+                    nullptr, nullptr, acc, gv, gm, gn, xbytes, wbytes, cls, Epi{});
       }
+      if (rc != 0) return rc;
     }
-  return (int)hipGetLastError();
+  return rc;
 }
 
 template <typename T>
@@ -4118,36 +4088,26 @@ int conv_dgrad_t(const void* dy, const void* wt, void* dx, int acc, const Geom& 
   Plan pl = plan_dgrad_v2(g);
   if constexpr (sizeof(T) == 2) {
     pl = plan_dgrad(g, dy, wt, dx, acc);
-    const bf16 *a = (const bf16*)dy, *b = (const bf16*)wt;
     switch (pl.k) {
       case Kern::V2:
       case Kern::V2_BIG: break;
       case Kern::S2_Q2S:
       case Kern::S2_Q2:
       case Kern::S2_MERGED:
-      case Kern::S2_CLASS: return launch_dgrad_s2(a, b, (bf16*)dx, acc, g, st, pl.k);
-      case Kern::HALO: return launch_halo<true>(a, b, (bf16*)dx, nullptr, nullptr, dgrad_view(g), st, acc);
-      default: return launch_v3<true>(a, b, nullptr, (bf16*)dx, nullptr, nullptr, acc, dgrad_view(g), st, Epi{}, pl);
+      case Kern::S2_CLASS: return launch_dgrad_s2(dy, wt, dx, acc, g, st, pl.k);
+      case Kern::HALO: return launch_halo<true>(dy, wt, dx, nullptr, nullptr, dgrad_view(g), st, acc);
+      default: return launch_v3<true>(dy, wt, nullptr, dx, nullptr, nullptr, acc, dgrad_view(g), st, Epi{}, pl);
     }
   }
-  if (pl.k == Kern::V2_BIG) return launch_dgrad<T, 128, 128>((const T*)dy, (const T*)wt, (T*)dx, acc, g, st);
-  return launch_dgrad<T, 64, 64>((const T*)dy, (const T*)wt, (T*)dx, acc, g, st);
-}
-inline int num_cus() {
-  static int n = [] {
-    int dev = 0, v = 0;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || v <= 0)
-      v = 256;
-    return v;
-  }();
-  return n;
+  if (pl.k == Kern::V2_BIG) return launch_dgrad<T, 128, 128>(dy, wt, dx, acc, g, st);
+  return launch_dgrad<T, 64, 64>(dy, wt, dx, acc, g, st);
 }
 
 // ---------------------------------------------------------------- weight-grad
 // tap-fused 3x3 s1 weight-grad (v3::conv_wgrad_tap) where it applies
 inline bool wgrad_tap_ok(const Geom& g, const void* x, const void* dy) {
   if (g.KH != 3 || g.KW != 3 || g.S != 1 || g.P != 1 || g.OH != g.H || g.OW != g.W) return false;
-  if (g.C % 16 != 0 || g.xps % 8 != 0 || g.yps % 8 != 0 || g.K % 8 != 0 || !aligned16(x) || !aligned16(dy)) return false;
+  if (g.C % 16 != 0 || !vec_ok(8, g.C, {g.xps, g.K, g.yps}, {}, {x, dy})) return false;
   // C % 32 == 16 (the space-to-depth stem, 16 channels) included: the upper half of the halo plane loads zeros
   // (yolov5s 3845 -> 3876 img/s against the v3n column tiles, profiles/r05/wgrad_tap16_ab.log)
   if (!fits_buf(x_bytes(g)) || !fits_buf(y_bytes(g))) return false;
@@ -4171,7 +4131,7 @@ WPlan plan_wgrad(const Geom& g, const void* x, const void* dy) {
   const long NP = (long)g.N * g.OH * g.OW;
   const int Ntot = g.KH * g.KW * g.C;
   if constexpr (sizeof(T) == 2) {
-    const bool vec = g.C % 8 == 0 && g.xps % 8 == 0 && g.K % 8 == 0 && g.yps % 8 == 0 && aligned16(x) && aligned16(dy);
+    const bool vec = vec_ok(8, g.C, {g.xps, g.K, g.yps}, {}, {x, dy});
     const int nm = wgrad_narrow_for(g, NP);
     const int nk = ceil_div(NP, 64);  // K steps of the column-tile kernels: 64 pixels
     const double NC = num_cus();
@@ -4217,45 +4177,40 @@ WPlan plan_wgrad(const Geom& g, const void* x, const void* dy) {
   return wgrad_split_v2(Kern::W_V2_64, ceil_div(g.K, 64) * ceil_div(Ntot, 64), nk);
 }
 
-inline void launch_wgrad_v3(const bf16* x, const bf16* dy, float* dw, const Geom& g, hipStream_t st, const WPlan& pl) {
-  const int Ntot = g.KH * g.KW * g.C;
-  const int gm = ceil_div(g.K, 128), gn = ceil_div(Ntot, 128);
-  const dim3 grid((unsigned)gm * gn, pl.splits);
-  const double xb = x_bytes(g), db = y_bytes(g);
-  if (fits_buf(xb) && fits_buf(db))
-    v3::conv_wgrad_v3<2, 1><<<grid, 256, 0, st>>>(x, dy, dw, pl.per, g, gm, gn, (unsigned)xb, (unsigned)db);
-  else
-    v3::conv_wgrad_v3<2, 0><<<grid, 256, 0, st>>>(x, dy, dw, pl.per, g, gm, gn, 0u, 0u);
+// The LDS-DMA weight-grads read x and dy through buffer descriptors of xb / db bytes; v3 and v3n keep a plain-pointer
+// form (BUF off, extents 0) for tensors past the descriptor range
+inline int launch_wgrad_v3(const void* x, const void* dy, float* dw, const Geom& g, hipStream_t st, const WPlan& pl) {
+  const int gm = ceil_div(g.K, 128), gn = ceil_div(g.KH * g.KW * g.C, 128);
+  const bool buf = fits_buf(x_bytes(g)) && fits_buf(y_bytes(g));
+  return by_flags(buf, [&](auto BUF) {
+    return launch(v3::conv_wgrad_v3<2, BUF.value>, dim3((unsigned)gm * gn, pl.splits), 256, 0, st, x, dy, dw, pl.per, g,
+                  gm, gn, buf ? (unsigned)x_bytes(g) : 0u, buf ? (unsigned)y_bytes(g) : 0u);
+  });
 }
 
-inline void launch_wgrad_v4(const bf16* x, const bf16* dy, float* dw, const Geom& g, hipStream_t st, const WPlan& pl) {
-  const int Ntot = g.KH * g.KW * g.C;
-  const int gm = ceil_div(g.K, 256), gn = ceil_div(Ntot, 128);
-  const dim3 grid((unsigned)gm * gn, pl.splits);
-  v3::conv_wgrad_v4<256, 128><<<grid, 512, 0, st>>>(x, dy, dw, pl.per, g, gm, gn, (unsigned)x_bytes(g),
-                                                    (unsigned)y_bytes(g));
+inline int launch_wgrad_v4(const void* x, const void* dy, float* dw, const Geom& g, hipStream_t st, const WPlan& pl) {
+  const int gm = ceil_div(g.K, 256), gn = ceil_div(g.KH * g.KW * g.C, 128);
+  return launch(v3::conv_wgrad_v4<256, 128>, dim3((unsigned)gm * gn, pl.splits), 512, 0, st, x, dy, dw, pl.per, g, gm,
+                gn, (unsigned)x_bytes(g), (unsigned)y_bytes(g));
 }
 
 template <int BM, int NP = 1>
-void launch_wgrad_tap(const bf16* x, const bf16* dy, float* dw, const Geom& g, hipStream_t st, const WPlan& pl) {
+int launch_wgrad_tap(const void* x, const void* dy, float* dw, const Geom& g, hipStream_t st, const WPlan& pl) {
   const int gm = ceil_div(g.K, BM), gn = ceil_div(g.C, 32 * NP);
   const int nk = g.N * ceil_div(g.OH, 8) * ceil_div(g.OW, 8);  // 8 x 8 patches
-  const dim3 grid((unsigned)gm * gn, pl.splits);
-  v3::conv_wgrad_tap<BM, NP><<<grid, 256, 0, st>>>(x, dy, dw, pl.per, g, gm, gn, nk, (unsigned)x_bytes(g),
-                                                   (unsigned)y_bytes(g));
+  return launch(v3::conv_wgrad_tap<BM, NP>, dim3((unsigned)gm * gn, pl.splits), 256, 0, st, x, dy, dw, pl.per, g, gm,
+                gn, nk, (unsigned)x_bytes(g), (unsigned)y_bytes(g));
 }
 
 template <int BM, int BN>
-void launch_wgrad_v3n(const bf16* x, const bf16* dy, float* dw, const Geom& g, hipStream_t st, const WPlan& pl) {
-  const int Ntot = g.KH * g.KW * g.C;
-  const int gm = ceil_div(g.K, BM), gn = ceil_div(Ntot, BN);
-  const dim3 grid((unsigned)gm * gn, pl.splits);
+int launch_wgrad_v3n(const void* x, const void* dy, float* dw, const Geom& g, hipStream_t st, const WPlan& pl) {
+  const int gm = ceil_div(g.K, BM), gn = ceil_div(g.KH * g.KW * g.C, BN);
   constexpr int NS = 3 * v3::WgradLdsN<BM, BN>::STAGE <= 80 * 1024 ? 3 : 2;  // keep 2 blocks per CU
-  const double xb = x_bytes(g), db = y_bytes(g);
-  if (fits_buf(xb) && fits_buf(db))
-    v3::conv_wgrad_v3n<BM, BN, NS, true><<<grid, BN, 0, st>>>(x, dy, dw, pl.per, g, gm, gn, (unsigned)xb, (unsigned)db);
-  else
-    v3::conv_wgrad_v3n<BM, BN, NS, false><<<grid, BN, 0, st>>>(x, dy, dw, pl.per, g, gm, gn, 0u, 0u);
+  const bool buf = fits_buf(x_bytes(g)) && fits_buf(y_bytes(g));
+  return by_flags(buf, [&](auto BUF) {
+    return launch(v3::conv_wgrad_v3n<BM, BN, NS, BUF.value>, dim3((unsigned)gm * gn, pl.splits), BN, 0, st, x, dy, dw,
+                  pl.per, g, gm, gn, buf ? (unsigned)x_bytes(g) : 0u, buf ? (unsigned)y_bytes(g) : 0u);
+  });
 }
 
 template <typename T>
@@ -4265,37 +4220,33 @@ int conv_wgrad_t(const void* x, const void* dy, float* dw, Geom g, hipStream_t s
   // stream-ordered launch's value), so the workspace is dropped
   if (pl.splits <= 1) g.dws = nullptr;
   if (!g.zeroed) (void)hipMemsetAsync(dw, 0, sizeof(float) * (size_t)g.K * g.KH * g.KW * g.C, st);
-  const bf16 *a = (const bf16*)x, *b = (const bf16*)dy;
   const bool k32 = g.K <= 32;
+  int rc;
   switch (sizeof(T) == 2 ? pl.k : Kern::V2) {
-    case Kern::W_TAP128: launch_wgrad_tap<128>(a, b, dw, g, st, pl); break;
-    case Kern::W_TAP64X2: launch_wgrad_tap<64, 2>(a, b, dw, g, st, pl); break;
-    case Kern::W_TAP64: launch_wgrad_tap<64>(a, b, dw, g, st, pl); break;
-    case Kern::W_V4: launch_wgrad_v4(a, b, dw, g, st, pl); break;
-    case Kern::W_V3: launch_wgrad_v3(a, b, dw, g, st, pl); break;
+    case Kern::W_TAP128: rc = launch_wgrad_tap<128>(x, dy, dw, g, st, pl); break;
+    case Kern::W_TAP64X2: rc = launch_wgrad_tap<64, 2>(x, dy, dw, g, st, pl); break;
+    case Kern::W_TAP64: rc = launch_wgrad_tap<64>(x, dy, dw, g, st, pl); break;
+    case Kern::W_V4: rc = launch_wgrad_v4(x, dy, dw, g, st, pl); break;
+    case Kern::W_V3: rc = launch_wgrad_v3(x, dy, dw, g, st, pl); break;
     case Kern::W_V3N256:
-      k32 ? launch_wgrad_v3n<32, 256>(a, b, dw, g, st, pl) : launch_wgrad_v3n<64, 256>(a, b, dw, g, st, pl);
+      rc = k32 ? launch_wgrad_v3n<32, 256>(x, dy, dw, g, st, pl) : launch_wgrad_v3n<64, 256>(x, dy, dw, g, st, pl);
       break;
     case Kern::W_V3N128:
-      k32 ? launch_wgrad_v3n<32, 128>(a, b, dw, g, st, pl) : launch_wgrad_v3n<64, 128>(a, b, dw, g, st, pl);
+      rc = k32 ? launch_wgrad_v3n<32, 128>(x, dy, dw, g, st, pl) : launch_wgrad_v3n<64, 128>(x, dy, dw, g, st, pl);
       break;
     default:
-      if (pl.k == Kern::W_V2_128) launch_wgrad<T, 128, 128>((const T*)x, (const T*)dy, dw, g, st, pl);
-      else launch_wgrad<T, 64, 64>((const T*)x, (const T*)dy, dw, g, st, pl);
+      rc = pl.k == Kern::W_V2_128 ? launch_wgrad<T, 128, 128>(x, dy, dw, g, st, pl)
+                                  : launch_wgrad<T, 64, 64>(x, dy, dw, g, st, pl);
   }
-  if (g.dws != nullptr)  // deterministic mode: sum the splits' workspace slabs into dw, in split order
-    wgrad_split_reduce<<<grid_cap(ceil_div(g.dws_slab, 256), 2048), 256, 0, st>>>(g.dws, dw, g.dws_slab, pl.splits);
-  return (int)hipGetLastError();
+  if (rc != 0 || g.dws == nullptr) return rc;
+  // deterministic mode: sum the splits' workspace slabs into dw, in split order
+  return launch(wgrad_split_reduce, grid_cap(ceil_div(g.dws_slab, 256), 2048), st, g.dws, dw, g.dws_slab, pl.splits);
 }
 
 }  // namespace
 
 // ================================================================ C ABI (include/dmayolo.h)
-#define DMY_WGRAD_OIHW 1
-#define DMY_WGRAD_ZEROED 2
-DMY_API int dmy_conv_wgrad_ex(int dtype, const void* x, const void* dy, float* dw, int N, int H, int W, int C,
-                              long xps, int K, int KH, int KW, int S, int P, int OH, int OW, long yps, int flags,
-                              void* stream);
+// A dtype other than 0 (fp32) or 1 (bf16) is refused with hipErrorInvalidValue before anything else is looked at.
 // BN partial rows of the forward epilogue: 2 per 128 (big tile) or 64 rows of M.  The v3 kernel's
 // 64-row wave rows number the same way (wave row wm of 256-row tile tm = row 4 tm + wm).
 // ---------------------------------------------------------------- fp8 operand preparation
@@ -4377,8 +4328,7 @@ __global__ void __launch_bounds__(256) wprep_fp8_kernel(const float* __restrict_
 
 inline bool fp8_fwd_ok(int C, int K, long yps, const void* x8, const void* w8, const void* y, double xbytes,
                        double wbytes) {
-  return C % 128 == 0 && K % 8 == 0 && K >= 32 && yps % 8 == 0 && aligned16(x8) && aligned16(w8) && aligned16(y) &&
-         xbytes < (double)v3::kBufOob && wbytes < (double)v3::kBufOob;
+  return C % 128 == 0 && K >= 32 && vec_ok(8, K, {yps}, {}, {x8, w8, y}) && fits_buf(xbytes) && fits_buf(wbytes);
 }
 
 DMY_API int dmy_conv_fwd_partial_rows(long M, int K) { return 2 * ceil_div(M, big_tile_rows(M, K) ? 128 : 64); }
@@ -4389,38 +4339,49 @@ DMY_API long dmy_conv_fwd_bound_rows(long M, int K) {
 }
 DMY_API long dmy_conv_fwd_last_rows() { return t_prow_last; }
 
+// fp32: the v2 tiles' rows; a dtype outside {0, 1}: 0
 DMY_API int dmy_conv_fwd_bn_rows(int dtype, const void* x, const void* w, const float* bias, const void* y,
                                  int N, int H, int W, int C, long xps, int K, int KH, int KW, int S, int P,
                                  int OH, int OW, long yps) {
+  if (dtype != 1) return dtype ? 0 : dmy_conv_fwd_partial_rows((long)N * OH * OW, K);
   const Geom g = make_geom(N, H, W, C, xps, K, KH, KW, S, P, OH, OW, yps);
-  if (!dtype) return dmy_conv_fwd_partial_rows((long)N * OH * OW, K);
   return (int)plan_fwd(g, x, w, bias, y, true, Epi{}, 0).rows;  // the training forward's own plan (conv_fwd_t)
+}
+
+// the forward entries' body: ps / pq = BN partials (training), ep = inference epilogue, ws = split-K workspace (bf16)
+static int fwd_entry(int dtype, const void* x, const void* w, const float* bias, void* y, float* ps, float* pq,
+                     const Geom& g, const Epi& ep, float* ws, long ws_elems, void* stream) {
+  return by_dtype(dtype, kInvalid, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    if ((long)g.N * g.OH * g.OW == 0 || g.K == 0) return 0;
+    return conv_fwd_t<T>(x, w, bias, y, ps, pq, g, (hipStream_t)stream, ep, ws, ws_elems);
+  });
 }
 
 DMY_API int dmy_conv_fwd(int dtype, const void* x, const void* w, const float* bias, void* y, float* psum, float* psq,
                          int N, int H, int W, int C, long xps, int K, int KH, int KW, int S, int P, int OH, int OW,
                          long yps, void* stream) {
-  Geom g = make_geom(N, H, W, C, xps, K, KH, KW, S, P, OH, OW, yps);
-  if ((long)N * OH * OW == 0 || K == 0) return 0;
-  return dtype ? conv_fwd_t<bf16>(x, w, bias, y, psum, psq, g, (hipStream_t)stream)
-               : conv_fwd_t<float>(x, w, bias, y, psum, psq, g, (hipStream_t)stream);
+  return fwd_entry(dtype, x, w, bias, y, psum, psq, make_geom(N, H, W, C, xps, K, KH, KW, S, P, OH, OW, yps), Epi{},
+                   nullptr, 0, stream);
 }
 
 DMY_API int dmy_conv_fwd_act(int dtype, const void* x, const void* w, const float* bias, void* y, int N, int H, int W,
                              int C, long xps, int K, int KH, int KW, int S, int P, int OH, int OW, long yps,
                              const float* scale, const float* shift, int act, const void* res, long rps,
                              void* stream) {
-  Geom g = make_geom(N, H, W, C, xps, K, KH, KW, S, P, OH, OW, yps);
-  if ((long)N * OH * OW == 0 || K == 0) return 0;
-  const Epi ep{scale, shift, res, rps, act, 1};
-  return dtype ? conv_fwd_t<bf16>(x, w, bias, y, nullptr, nullptr, g, (hipStream_t)stream, ep)
-               : conv_fwd_t<float>(x, w, bias, y, nullptr, nullptr, g, (hipStream_t)stream, ep);
+  return fwd_entry(dtype, x, w, bias, y, nullptr, nullptr, make_geom(N, H, W, C, xps, K, KH, KW, S, P, OH, OW, yps),
+                   Epi{scale, shift, res, rps, act, 1}, nullptr, 0, stream);  // the epilogue always on
+}
+
+// the inference epilogue of the entries that may go without one: on only when there is something to apply
+static Epi epi_if_any(const float* scale, const float* shift, int act, const void* res, long rps) {
+  return Epi{scale, shift, res, rps, act, scale != nullptr || res != nullptr || act != 0 ? 1 : 0};
 }
 
 // ws: at least dmy_fp8_quant_ws_elems() floats; ws[0] receives the amax the quantisation used
 DMY_API long dmy_fp8_quant_ws_elems() { return 1 + kF8Blocks; }
 DMY_API int dmy_fp8_quant(const void* x, long rows, int C, long xps, void* x8, float* ws, void* stream) {
-  if (C % 8 != 0 || xps % 8 != 0 || !aligned16(x) || rows * (C / 8) >= (1L << 31)) return (int)hipErrorInvalidValue;
+  if (!vec_ok(8, C, {xps}, {}, {x}) || rows * (C / 8) >= (1L << 31)) return kInvalid;
   hipStream_t st = (hipStream_t)stream;
   const unsigned nvec = (unsigned)(rows * (C / 8));
   if (nvec == 0) {
@@ -4428,9 +4389,8 @@ DMY_API int dmy_fp8_quant(const void* x, long rows, int C, long xps, void* x8, f
     return (int)hipGetLastError();
   }
   const int grid = grid_cap(ceil_div(nvec, 256), kF8Blocks);
-  fp8_blockmax_kernel<<<grid, 256, 0, st>>>((const bf16*)x, nvec, C / 8, xps, ws + 1);
-  fp8_quant_kernel<<<grid, 256, 0, st>>>((const bf16*)x, nvec, C / 8, xps, (unsigned char*)x8, ws + 1, grid, ws);
-  return (int)hipGetLastError();
+  const int rc = launch(fp8_blockmax_kernel, grid, st, x, nvec, C / 8, xps, ws + 1);
+  return rc ? rc : launch(fp8_quant_kernel, grid, st, x, nvec, C / 8, xps, x8, ws + 1, grid, ws);
 }
 
 DMY_API int dmy_conv_wprep_fp8(const float* w_oihw, void* w8, float* wscale, int K, int C, int KH, int KW,
@@ -4451,36 +4411,24 @@ DMY_API int dmy_conv_fwd_fp8(const void* x8, const void* w8, const float* xamax,
   const long M = (long)N * OH * OW;
   if (M == 0 || K == 0) return 0;
   const double xb = (double)N * H * W * C, wb = (double)K * KH * KW * C;
-  if (!fp8_fwd_ok(C, K, yps, x8, w8, y, xb, wb) || (res && (rps % 8 != 0 || !aligned16(res))))
-    return (int)hipErrorInvalidValue;
-  const Epi ep{scale, shift, res, rps, act, scale != nullptr || res != nullptr || act != 0 ? 1 : 0};
-  const bool p1 = KH == 1 && KW == 1 && S == 1 && P == 0;
-  hipStream_t st = (hipStream_t)stream;
-  const unsigned xbytes = (unsigned)xb, wbytes = (unsigned)wb;
-  const unsigned char *a = (const unsigned char*)x8, *b = (const unsigned char*)w8;
-#define F8_GO(BM, BN, NS)                                                                                          \
-  {                                                                                                                \
-    const int gm = ceil_div(M, BM), gn = ceil_div(K, BN);                                                          \
-    if (p1)                                                                                                        \
-      v3::conv_fwd_f8<BM, BN, NS, true><<<(unsigned)gm * gn, BM * BN / 64, 0, st>>>(                                \
-          a, b, xamax, wscale, bias, (bf16*)y, psum, psq, g, gm, gn, xbytes, wbytes, ep);                          \
-    else                                                                                                           \
-      v3::conv_fwd_f8<BM, BN, NS, false><<<(unsigned)gm * gn, BM * BN / 64, 0, st>>>(                               \
-          a, b, xamax, wscale, bias, (bf16*)y, psum, psq, g, gm, gn, xbytes, wbytes, ep);                          \
-  }
-  if (K > 64) F8_GO(256, 128, 3)
-  else F8_GO(256, 64, 2)
-#undef F8_GO
-  return (int)hipGetLastError();
+  if (!fp8_fwd_ok(C, K, yps, x8, w8, y, xb, wb) || !res_ok(res, rps)) return kInvalid;
+  const Epi ep = epi_if_any(scale, shift, act, res, rps);
+  // 256 x 128 tiles with 3 stages above 64 output channels, else 256 x 64 with 2
+  return by_flags(K > 64, is_p1(g), [&](auto BIG, auto P1) {
+    constexpr int BN = BIG.value ? 128 : 64, NS = BIG.value ? 3 : 2;
+    const int gm = ceil_div(M, 256), gn = ceil_div(K, BN);
+    return launch(v3::conv_fwd_f8<256, BN, NS, P1.value>, (unsigned)gm * gn, 256 * BN / 64, 0, stream, x8, w8, xamax,
+                  wscale, bias, y, psum, psq, g, gm, gn, (unsigned)xb, (unsigned)wb, ep);
+  });
 }
 
 // Inference forward with a split-K workspace for small M (batch-1 detect): dmy_conv_fwd_act semantics; when
 // dmy_conv_fwd_splitk_elems > 0 for the same arguments, a workspace of that many floats lets the small-M layers
 // split their reduction over the chip (0: the call is dmy_conv_fwd_act).  scale == shift == res == nullptr and
-// act == 0 is the plain forward (no BN partials).
+// act == 0 is the plain forward (no BN partials).  fp32 never splits, and a dtype outside {0, 1} answers 0 too.
 DMY_API long dmy_conv_fwd_splitk_elems(int dtype, const void* x, const void* w, const void* y, int N, int H, int W,
                                        int C, long xps, int K, int KH, int KW, int S, int P, int OH, int OW, long yps) {
-  if (!dtype) return 0;
+  if (dtype != 1) return 0;
   return splitk_elems(make_geom(N, H, W, C, xps, K, KH, KW, S, P, OH, OW, yps), x, w, y);
 }
 
@@ -4488,105 +4436,114 @@ DMY_API int dmy_conv_fwd_act_ws(int dtype, const void* x, const void* w, const f
                                 int W, int C, long xps, int K, int KH, int KW, int S, int P, int OH, int OW, long yps,
                                 const float* scale, const float* shift, int act, const void* res, long rps, float* ws,
                                 long ws_elems, void* stream) {
-  Geom g = make_geom(N, H, W, C, xps, K, KH, KW, S, P, OH, OW, yps);
-  if ((long)N * OH * OW == 0 || K == 0) return 0;
-  const Epi ep{scale, shift, res, rps, act, scale != nullptr || res != nullptr || act != 0 ? 1 : 0};
-  return dtype ? conv_fwd_t<bf16>(x, w, bias, y, nullptr, nullptr, g, (hipStream_t)stream, ep, ws, ws_elems)
-               : conv_fwd_t<float>(x, w, bias, y, nullptr, nullptr, g, (hipStream_t)stream, ep);
+  return fwd_entry(dtype, x, w, bias, y, nullptr, nullptr, make_geom(N, H, W, C, xps, K, KH, KW, S, P, OH, OW, yps),
+                   epi_if_any(scale, shift, act, res, rps), ws, ws_elems, stream);
 }
 
 DMY_API int dmy_conv_dgrad(int dtype, const void* dy, const void* wt, void* dx, int accumulate, int N, int H, int W,
                            int C, long xps, int K, int KH, int KW, int S, int P, int OH, int OW, long yps,
                            void* stream) {
-  Geom g = make_geom(N, H, W, C, xps, K, KH, KW, S, P, OH, OW, yps);
-  if ((long)N * H * W == 0 || C == 0) return 0;
-  if (S > 2) return (int)hipErrorInvalidValue;
-  return dtype ? conv_dgrad_t<bf16>(dy, wt, dx, accumulate, g, (hipStream_t)stream)
-               : conv_dgrad_t<float>(dy, wt, dx, accumulate, g, (hipStream_t)stream);
+  return by_dtype(dtype, kInvalid, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    if ((long)N * H * W == 0 || C == 0) return 0;
+    if (S > 2) return kInvalid;
+    const Geom g = make_geom(N, H, W, C, xps, K, KH, KW, S, P, OH, OW, yps);
+    return conv_dgrad_t<T>(dy, wt, dx, accumulate, g, (hipStream_t)stream);
+  });
+}
+
+// the weight-grad entries' body: g carries the flags; det = deterministic mode, whose splits (when more than one)
+// store to the workspace ws of ws_elems floats instead of fp32 atomics
+static int wgrad_entry(int dtype, const void* x, const void* dy, float* dw, Geom g, void* stream, bool det = false,
+                       float* ws = nullptr, long ws_elems = 0) {
+  return by_dtype(dtype, kInvalid, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    const long slab = (long)g.K * g.KH * g.KW * g.C;
+    if (const int splits = det ? plan_wgrad<T>(g, x, dy).splits : 1; splits > 1) {
+      if (ws == nullptr || ws_elems < splits * slab) return kInvalid;
+      g.dws = ws;
+      g.dws_slab = slab;
+    }
+    return conv_wgrad_t<T>(x, dy, dw, g, (hipStream_t)stream);
+  });
 }
 
 DMY_API int dmy_conv_wgrad(int dtype, const void* x, const void* dy, float* dw_ohwi, int N, int H, int W, int C,
                            long xps, int K, int KH, int KW, int S, int P, int OH, int OW, long yps, void* stream) {
-  return dmy_conv_wgrad_ex(dtype, x, dy, dw_ohwi, N, H, W, C, xps, K, KH, KW, S, P, OH, OW, yps, 0, stream);
+  return wgrad_entry(dtype, x, dy, dw_ohwi, make_geom(N, H, W, C, xps, K, KH, KW, S, P, OH, OW, yps), stream);
 }
 
 DMY_API int dmy_conv_wgrad_ex(int dtype, const void* x, const void* dy, float* dw, int N, int H, int W, int C,
                               long xps, int K, int KH, int KW, int S, int P, int OH, int OW, long yps, int flags,
                               void* stream) {
-  Geom g = make_geom(N, H, W, C, xps, K, KH, KW, S, P, OH, OW, yps);
-  g.oihw = flags & DMY_WGRAD_OIHW ? 1 : 0;
-  g.zeroed = flags & DMY_WGRAD_ZEROED ? 1 : 0;
-  return dtype ? conv_wgrad_t<bf16>(x, dy, dw, g, (hipStream_t)stream)
-               : conv_wgrad_t<float>(x, dy, dw, g, (hipStream_t)stream);
+  return wgrad_entry(dtype, x, dy, dw, make_geom(N, H, W, C, xps, K, KH, KW, S, P, OH, OW, yps, flags), stream);
 }
 
-// deterministic weight-grad: fp32 workspace elements it needs (0 = the dispatch uses one split: no workspace)
+// deterministic weight-grad: fp32 workspace elements it needs (0 = the dispatch uses one split: no workspace; 0 also
+// for a dtype outside {0, 1})
 DMY_API long dmy_conv_wgrad_ws_elems(int dtype, const void* x, const void* dy, int N, int H, int W, int C, long xps,
                                      int K, int KH, int KW, int S, int P, int OH, int OW, long yps, int flags) {
   (void)flags;  // the output layout and the memset do not change the split
   const Geom g = make_geom(N, H, W, C, xps, K, KH, KW, S, P, OH, OW, yps);
-  const int splits = dtype ? plan_wgrad<bf16>(g, x, dy).splits : plan_wgrad<float>(g, x, dy).splits;
+  const int splits = by_dtype(dtype, 0, [&](auto tag) { return plan_wgrad<typename decltype(tag)::type>(g, x, dy).splits; });
   return splits > 1 ? (long)splits * K * KH * KW * C : 0;
 }
 
-// The kernel (DMY_KERN_*) the dispatch takes for these arguments; the pointers are only tested for alignment.
+// The kernel (DMY_KERN_*) the dispatch takes for these arguments; the pointers are only tested for alignment.  -1 for
+// a dtype outside {0, 1}, as for an unknown pass.
 DMY_API int dmy_conv_route(int pass, int dtype, const void* a, const void* b, const void* c, int N, int H, int W, int C,
                            long xps, int K, int KH, int KW, int S, int P, int OH, int OW, long yps, int acc) {
   static_assert((int)Kern::V2 == DMY_KERN_V2 && (int)Kern::S2_CLASS == DMY_KERN_S2_CLASS &&
                     (int)Kern::W_V4 == DMY_KERN_W_V4 && (int)Kern::W_V2_64 == DMY_KERN_W_V2_64,
                 "Kern and the header's DMY_KERN_* codes number alike");
   const Geom g = make_geom(N, H, W, C, xps, K, KH, KW, S, P, OH, OW, yps);
-  switch (pass) {
-    case 0:  // training forward without bias: a = x, b = w_ohwi, c = y
-      return (int)(dtype ? plan_fwd(g, a, b, nullptr, c, true, Epi{}, 0).k : Kern::V2);
-    case 1:  // data-grad: a = dy, b = w_ihwo, c = dx
-      return S > 2 ? -1 : (int)(dtype ? plan_dgrad(g, a, b, c, acc) : plan_dgrad_v2(g)).k;
-    case 2:  // weight-grad: a = x, b = dy
-      return (int)(dtype ? plan_wgrad<bf16>(g, a, b) : plan_wgrad<float>(g, a, b)).k;
-    default: return -1;
-  }
+  return by_dtype(dtype, -1, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    constexpr bool h = sizeof(T) == 2;  // the LDS-DMA plans are bf16's; fp32 stays on the v2 tiles
+    switch (pass) {
+      case 0:  // training forward without bias: a = x, b = w_ohwi, c = y
+        return (int)(h ? plan_fwd(g, a, b, nullptr, c, true, Epi{}, 0).k : Kern::V2);
+      case 1:  // data-grad: a = dy, b = w_ihwo, c = dx
+        return S > 2 ? -1 : (int)(h ? plan_dgrad(g, a, b, c, acc) : plan_dgrad_v2(g)).k;
+      case 2:  // weight-grad: a = x, b = dy
+        return (int)plan_wgrad<T>(g, a, b).k;
+      default: return -1;
+    }
+  });
 }
 
 DMY_API int dmy_conv_wgrad_det(int dtype, const void* x, const void* dy, float* dw, int N, int H, int W, int C,
                                long xps, int K, int KH, int KW, int S, int P, int OH, int OW, long yps, int flags,
                                float* ws, long ws_elems, void* stream) {
-  const long need = dmy_conv_wgrad_ws_elems(dtype, x, dy, N, H, W, C, xps, K, KH, KW, S, P, OH, OW, yps, flags);
-  if (need > 0 && (ws == nullptr || ws_elems < need)) return (int)hipErrorInvalidValue;
-  Geom g = make_geom(N, H, W, C, xps, K, KH, KW, S, P, OH, OW, yps);
-  g.oihw = flags & DMY_WGRAD_OIHW ? 1 : 0;
-  g.zeroed = flags & DMY_WGRAD_ZEROED ? 1 : 0;
-  if (need > 0) {
-    g.dws = ws;
-    g.dws_slab = (long)K * KH * KW * C;
-  }
-  return dtype ? conv_wgrad_t<bf16>(x, dy, dw, g, (hipStream_t)stream)
-               : conv_wgrad_t<float>(x, dy, dw, g, (hipStream_t)stream);
+  return wgrad_entry(dtype, x, dy, dw, make_geom(N, H, W, C, xps, K, KH, KW, S, P, OH, OW, yps, flags), stream, true,
+                     ws, ws_elems);
 }
 
 DMY_API int dmy_conv_wprep(int dtype, const float* w_oihw, void* w_ohwi, void* w_ihwo, int K, int C, int Cp, int KH,
                            int KW, void* stream) {
   const long total = (long)K * Cp * KH * KW;
   const int grid = grid_cap(ceil_div(total, 256), 1024);
-  if (dtype) wprep_kernel<bf16><<<grid, 256, 0, (hipStream_t)stream>>>(w_oihw, (bf16*)w_ohwi, (bf16*)w_ihwo, K, C, Cp, KH, KW);
-  else wprep_kernel<float><<<grid, 256, 0, (hipStream_t)stream>>>(w_oihw, (float*)w_ohwi, (float*)w_ihwo, K, C, Cp, KH, KW);
-  return (int)hipGetLastError();
+  return by_dtype(dtype, kInvalid, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    return launch(wprep_kernel<T>, grid, stream, w_oihw, w_ohwi, w_ihwo, K, C, Cp, KH, KW);
+  });
 }
 
 // descs: device array of n WprepDesc {w, wf, wt (nullable), K, C, KH, KW} (40 bytes each, include/dmayolo.h)
 DMY_API int dmy_conv_wprep_multi(int dtype, const void* descs, int n, void* stream) {
-  if (n <= 0) return 0;
   static_assert(sizeof(WprepDesc) == 40, "WprepDesc layout is part of the C ABI");
-  const dim3 grid(128, n);
-  if (dtype) wprep_multi_kernel<bf16><<<grid, 256, 0, (hipStream_t)stream>>>((const WprepDesc*)descs);
-  else wprep_multi_kernel<float><<<grid, 256, 0, (hipStream_t)stream>>>((const WprepDesc*)descs);
-  return (int)hipGetLastError();
+  return by_dtype(dtype, kInvalid, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    return n <= 0 ? 0 : launch(wprep_multi_kernel<T>, dim3(128, n), stream, descs);
+  });
 }
 
 DMY_API int dmy_conv_wprep_s2d(int dtype, const float* w_oihw, void* w_s2d, int K, int C, int Cs, void* stream) {
   const int grid = grid_cap(ceil_div((long)K * 9 * Cs, 256), 1024);
-  if (dtype) wprep_s2d_kernel<bf16><<<grid, 256, 0, (hipStream_t)stream>>>(w_oihw, (bf16*)w_s2d, K, C, Cs);
-  else wprep_s2d_kernel<float><<<grid, 256, 0, (hipStream_t)stream>>>(w_oihw, (float*)w_s2d, K, C, Cs);
-  return (int)hipGetLastError();
+  return by_dtype(dtype, kInvalid, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    return launch(wprep_s2d_kernel<T>, grid, stream, w_oihw, w_s2d, K, C, Cs);
+  });
 }
 
 DMY_API int dmy_conv_wgrad_s2d_to_oihw(const float* dw_s2d, float* dw_oihw, int K, int C, int Cs, void* stream) {

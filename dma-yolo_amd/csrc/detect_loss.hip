@@ -15,7 +15,7 @@
 //    utils/loss.py:207-212 (per-level objectness balance, updated by the finalize kernel on the device).  These are
 //    the EX = true instances of the level kernels; the EX = false instances are the plain-BCE path, unchanged.
 // Everything stays on device: target counts are read by the kernels, never by the host.
-#include "common.h"
+#include "launch.h"
 #include "dual.h"
 
 namespace {
@@ -561,20 +561,45 @@ __global__ void loss_grad_kernel(const float* __restrict__ G, const float* __res
     dp[i] = from_f<T>(G[i] * u);
 }
 
+// one level of the YOLO loss (FOCAL: the focal element and the device-side balance of LossEx): target pass, combine
+// of the per-cell lists, objectness pass
+template <bool FOCAL>
+int loss_level(int dtype, const void* p, const LossCfg& cfg, const LossEx& ex, const int* tb, const int* ta,
+               const int* tgj, const int* tgi, const int* tcls, const float* tbox, const float* anch, const int* count,
+               int cap, float* G, float* tobj, float* part, float* tgrad, int* links, void* stream) {
+  return by_dtype(dtype, kInvalid, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    const int gt = grid_cap(ceil_div(cap, 256), 1024);
+    const long cells = (long)cfg.N * cfg.na * cfg.H * cfg.W;
+    int* head = links;
+    int* nxt = links + cells;
+    (void)hipMemsetAsync(head, 0xff, sizeof(int) * (size_t)cells, (hipStream_t)stream);  // empty lists (-1)
+    int rc = launch(loss_targets_kernel<T, FOCAL>, gt, stream, p, cfg, ex, tb, ta, tgj, tgi, tcls, tbox, anch, count,
+                    tgrad, head, nxt, tobj, part);
+    if (rc == 0) rc = launch(loss_combine_kernel, gt, stream, cfg, tb, ta, tgj, tgi, count, tgrad, head, nxt, G);
+    if (rc != 0) return rc;
+    return launch(loss_obj_kernel<T, FOCAL>, grid_cap(ceil_div(cells, 256), LOSS_PMAX), stream, p, cfg, ex, tobj, G,
+                  part);
+  });
+}
+
 }  // namespace
 
+// A dtype other than 0 (fp32) or 1 (bf16) is refused with hipErrorInvalidValue before anything else is looked at.
 DMY_API int dmy_detect_decode(int dtype, const void* y, long sb, long sh, long sw, int N, int H, int W, int na, int no,
                               float stride, const float* anchors, float* z, long zoff, long ztotal, void* stream) {
   const long total = (long)N * na * H * W * no;
-  const int g = grid_cap(ceil_div(total, 256), 8192);
-  if (dtype) decode_kernel<bf16><<<g, 256, 0, (hipStream_t)stream>>>((const bf16*)y, sb, sh, sw, N, H, W, na, no, stride, anchors, z, zoff, ztotal);
-  else decode_kernel<float><<<g, 256, 0, (hipStream_t)stream>>>((const float*)y, sb, sh, sw, N, H, W, na, no, stride, anchors, z, zoff, ztotal);
-  return (int)hipGetLastError();
+  return by_dtype(dtype, kInvalid, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    return launch(decode_kernel<T>, grid_cap(ceil_div(total, 256), 8192), stream, y, sb, sh, sw, N, H, W, na, no, stride,
+                  anchors, z, zoff, ztotal);
+  });
 }
 
 DMY_API int dmy_detect_decode_levels(int dtype, int nl, const void* const* ys, const long* strides, const int* hw,
                                      const float* lvl_stride, int N, int na, int no, const float* anchors, float* z,
                                      long ztotal, void* stream) {
+  if (dtype != 0 && dtype != 1) return kInvalid;
   if (nl < 1 || nl > kDecLevels) return (int)hipErrorInvalidValue;
   DecTab tab{};
   tab.nl = nl;
@@ -594,15 +619,16 @@ DMY_API int dmy_detect_decode_levels(int dtype, int nl, const void* const* ys, c
   }
   if (zoff != ztotal) return (int)hipErrorInvalidValue;
   const int g = grid_cap(ceil_div(tab.cum[nl], 256), 8192);
-  if (dtype) decode_levels_kernel<bf16><<<g, 256, 0, (hipStream_t)stream>>>(tab, N, na, no, anchors, z, ztotal);
-  else decode_levels_kernel<float><<<g, 256, 0, (hipStream_t)stream>>>(tab, N, na, no, anchors, z, ztotal);
-  return (int)hipGetLastError();
+  return by_dtype(dtype, kInvalid, [&](auto tag) {
+    return launch(decode_levels_kernel<typename decltype(tag)::type>, g, stream, tab, N, na, no, anchors, z, ztotal);
+  });
 }
 
 DMY_API int dmy_detect_decode_tta(int dtype, int nl, const void* const* ys, const long* strides, const int* hw,
                                   const float* lvl_stride, int N, int na, int no, const float* anchors, float* z,
                                   long ztotal, float scale, int flip, float img_h, float img_w, int level_mask,
                                   long zoff, void* stream) {
+  if (dtype != 0 && dtype != 1) return kInvalid;
   if (nl < 1 || nl > kDecLevels || !(scale > 0.f) || (flip != 0 && flip != 2 && flip != 3) || zoff < 0)
     return (int)hipErrorInvalidValue;
   TtaTab tt{};
@@ -628,10 +654,10 @@ DMY_API int dmy_detect_decode_tta(int dtype, int nl, const void* const* ys, cons
   if (k == 0) return (int)hipSuccess;
   tab.nl = k;
   const int g = grid_cap(ceil_div(tab.cum[k], 256), 8192);
-  hipStream_t st = (hipStream_t)stream;
-  if (dtype) decode_tta_kernel<bf16><<<g, 256, 0, st>>>(tt, N, na, no, anchors, z, ztotal, scale, flip, img_h, img_w);
-  else decode_tta_kernel<float><<<g, 256, 0, st>>>(tt, N, na, no, anchors, z, ztotal, scale, flip, img_h, img_w);
-  return (int)hipGetLastError();
+  return by_dtype(dtype, kInvalid, [&](auto tag) {
+    return launch(decode_tta_kernel<typename decltype(tag)::type>, g, stream, tt, N, na, no, anchors, z, ztotal, scale,
+                  flip, img_h, img_w);
+  });
 }
 
 DMY_API int dmy_build_targets(const float* targets, int nt, const float* anchors, int na, int H, int W, float anchor_t,
@@ -653,25 +679,9 @@ DMY_API int dmy_yolo_loss_level(int dtype, const void* p, long sb, long sa, long
                                 const int* ta, const int* tgj, const int* tgi, const int* tcls, const float* tbox,
                                 const float* anch, const int* count, int cap, float* G, float* tobj, float* part,
                                 float* tgrad, int* links, void* stream) {
-  hipStream_t st = (hipStream_t)stream;
-  LossCfg cfg{box_gain, obj_gain, cls_gain, cls_pw, obj_pw, cp, cn, balance, bs, nc, na, no, N, H, W, sb, sa, sh, sw};
-  const int gt = grid_cap(ceil_div(cap, 256), 1024);
-  const long cells = (long)N * na * H * W;
-  const int go = grid_cap(ceil_div(cells, 256), LOSS_PMAX);
-  int* head = links;
-  int* nxt = links + cells;
-  (void)hipMemsetAsync(head, 0xff, sizeof(int) * (size_t)cells, st);  // empty lists (-1)
-  const LossEx ex{};
-  if (dtype)
-    loss_targets_kernel<bf16, false><<<gt, 256, 0, st>>>((const bf16*)p, cfg, ex, tb, ta, tgj, tgi, tcls, tbox, anch,
-                                                         count, tgrad, head, nxt, tobj, part);
-  else
-    loss_targets_kernel<float, false><<<gt, 256, 0, st>>>((const float*)p, cfg, ex, tb, ta, tgj, tgi, tcls, tbox, anch,
-                                                          count, tgrad, head, nxt, tobj, part);
-  loss_combine_kernel<<<gt, 256, 0, st>>>(cfg, tb, ta, tgj, tgi, count, tgrad, head, nxt, G);
-  if (dtype) loss_obj_kernel<bf16, false><<<go, 256, 0, st>>>((const bf16*)p, cfg, ex, tobj, G, part);
-  else loss_obj_kernel<float, false><<<go, 256, 0, st>>>((const float*)p, cfg, ex, tobj, G, part);
-  return (int)hipGetLastError();
+  const LossCfg cfg{box_gain, obj_gain, cls_gain, cls_pw, obj_pw, cp, cn, balance, bs, nc, na, no, N, H, W, sb, sa, sh, sw};
+  return loss_level<false>(dtype, p, cfg, LossEx{}, tb, ta, tgj, tgi, tcls, tbox, anch, count, cap, G, tobj, part, tgrad,
+                           links, stream);
 }
 
 // dmy_yolo_loss_level with the focal element (fl_gamma > 0; 0 = plain BCE) and the balance read from balance[level]
@@ -684,27 +694,12 @@ DMY_API int dmy_yolo_loss_level_focal(int dtype, const void* p, long sb, long sa
                                       const int* tgi, const int* tcls, const float* tbox, const float* anch,
                                       const int* count, int cap, float* G, float* tobj, float* part, float* tgrad,
                                       int* links, void* stream) {
-  if (!(fl_gamma >= 0.f) || level < 0 || level >= kBalLevels || balance == nullptr) return (int)hipErrorInvalidValue;
-  hipStream_t st = (hipStream_t)stream;
-  LossCfg cfg{box_gain, obj_gain, cls_gain, cls_pw, obj_pw, cp, cn, 0.f, bs, nc, na, no, N, H, W, sb, sa, sh, sw};
+  if (dtype != 0 && dtype != 1) return kInvalid;
+  if (!(fl_gamma >= 0.f) || level < 0 || level >= kBalLevels || balance == nullptr) return kInvalid;
+  const LossCfg cfg{box_gain, obj_gain, cls_gain, cls_pw, obj_pw, cp, cn, 0.f, bs, nc, na, no, N, H, W, sb, sa, sh, sw};
   const int gmode = fl_gamma == 0.f ? 0 : fl_gamma == 1.f ? 1 : fl_gamma == 1.5f ? 2 : fl_gamma == 2.f ? 3 : 4;
-  const LossEx ex{balance, level, gmode, fl_gamma};
-  const int gt = grid_cap(ceil_div(cap, 256), 1024);
-  const long cells = (long)N * na * H * W;
-  const int go = grid_cap(ceil_div(cells, 256), LOSS_PMAX);
-  int* head = links;
-  int* nxt = links + cells;
-  (void)hipMemsetAsync(head, 0xff, sizeof(int) * (size_t)cells, st);  // empty lists (-1)
-  if (dtype)
-    loss_targets_kernel<bf16, true><<<gt, 256, 0, st>>>((const bf16*)p, cfg, ex, tb, ta, tgj, tgi, tcls, tbox, anch,
-                                                        count, tgrad, head, nxt, tobj, part);
-  else
-    loss_targets_kernel<float, true><<<gt, 256, 0, st>>>((const float*)p, cfg, ex, tb, ta, tgj, tgi, tcls, tbox, anch,
-                                                         count, tgrad, head, nxt, tobj, part);
-  loss_combine_kernel<<<gt, 256, 0, st>>>(cfg, tb, ta, tgj, tgi, count, tgrad, head, nxt, G);
-  if (dtype) loss_obj_kernel<bf16, true><<<go, 256, 0, st>>>((const bf16*)p, cfg, ex, tobj, G, part);
-  else loss_obj_kernel<float, true><<<go, 256, 0, st>>>((const float*)p, cfg, ex, tobj, G, part);
-  return (int)hipGetLastError();
+  return loss_level<true>(dtype, p, cfg, LossEx{balance, level, gmode, fl_gamma}, tb, ta, tgj, tgi, tcls, tbox, anch,
+                          count, cap, G, tobj, part, tgrad, links, stream);
 }
 
 DMY_API int dmy_yolo_loss_finalize(const float* part, int nl, float box, float obj, float cls, float bs, float* loss,
@@ -723,10 +718,9 @@ DMY_API int dmy_yolo_loss_finalize_balance(const float* part, int nl, float box,
 }
 
 DMY_API int dmy_loss_grad(int dtype, const float* G, const float* up, void* dp, long n, void* stream) {
-  const int g = grid_cap(ceil_div(n, 256), 4096);
-  if (dtype) loss_grad_kernel<bf16><<<g, 256, 0, (hipStream_t)stream>>>(G, up, (bf16*)dp, n);
-  else loss_grad_kernel<float><<<g, 256, 0, (hipStream_t)stream>>>(G, up, (float*)dp, n);
-  return (int)hipGetLastError();
+  return by_dtype(dtype, kInvalid, [&](auto tag) {
+    return launch(loss_grad_kernel<typename decltype(tag)::type>, grid_cap(ceil_div(n, 256), 4096), stream, G, up, dp, n);
+  });
 }
 
 // SIoU of n xywh box pairs through the loss kernel's own siou(): value and d(iou)/d(b1) (test entry)

@@ -3,6 +3,8 @@
 #pragma once
 #include "common.h"
 #include <initializer_list>
+#include <tuple>
+#include <type_traits>
 
 template <typename T> struct DType { using type = T; };
 
@@ -22,12 +24,25 @@ template <typename F> inline int by_dtype_vec(int dtype, bool vec, int refuse, F
     return vec ? f(tag, Width<Traits<T>::VW>{}) : f(tag, Width<1>{});
   });
 }
+// by_flags(b0[, b1[, b2]], f): f(std::bool_constant<b0>{}, ...), the runtime bools turned into tags whose ::value picks
+// a kernel's bool template arguments.  f is a generic lambda that holds the one launch and returns the entry's int.
+template <size_t I = 0, typename Tup, typename... Tag> inline int by_flags_(const Tup& a, Tag... tags) {
+  if constexpr (I + 1 == std::tuple_size_v<Tup>) return std::get<I>(a)(tags...);
+  else if (std::get<I>(a)) return by_flags_<I + 1>(a, tags..., std::true_type{});
+  else return by_flags_<I + 1>(a, tags..., std::false_type{});
+}
+template <typename... A> inline int by_flags(A&&... a) { return by_flags_(std::forward_as_tuple(a...)); }
 
-// k<<<grid, 256, 0, stream>>>(args...) and the launch status.  Each argument is converted to the kernel's own parameter
-// type, so an entry passes its void pointers as they are: the kernel's signature, not a cast at the call, types them.
-template <typename... P, typename... A> inline int launch(void (*k)(P...), dim3 grid, void* stream, A... args) {
-  k<<<grid, 256, 0, (hipStream_t)stream>>>(static_cast<P>(args)...);
+// k<<<grid, block, lds, stream>>>(args...) and the launch status.  Each argument is converted to the kernel's own
+// parameter type, so an entry passes its void pointers as they are: the kernel's signature, not a cast at the call,
+// types them.  The short form is the streaming kernels' 256 threads and no dynamic LDS.
+template <typename... P, typename... A>
+inline int launch(void (*k)(P...), dim3 grid, dim3 block, size_t lds, void* stream, A... args) {
+  k<<<grid, block, lds, (hipStream_t)stream>>>(static_cast<P>(args)...);
   return (int)hipGetLastError();
+}
+template <typename... P, typename... A> inline int launch(void (*k)(P...), dim3 grid, void* stream, A... args) {
+  return launch(k, grid, 256, 0, stream, args...);
 }
 
 inline int vec_width(int dtype) { return dtype ? 8 : 4; }  // elements per 16-byte vector

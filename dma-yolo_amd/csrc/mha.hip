@@ -22,7 +22,7 @@
 //     one query: exactly the B fragment of O^T = V^T P^T.  The softmax statistics and the O^T
 //     accumulator rows therefore belong to the same lane (query = lane & 15): no shuffles beyond
 //     the 4-lane-group row reductions.
-#include "common.h"
+#include "launch.h"
 
 namespace {
 
@@ -615,84 +615,73 @@ __global__ void dropout_kernel(const T* __restrict__ x, long xps, T* __restrict_
   }
 }
 
-inline bool mfma_ok(int dtype, const MhaGeom& g, const void* const* ps) {
-  if (!dtype || !(g.d == 32 || g.d == 64 || g.d == 128)) return false;
-  if (g.qps % 8 || g.kps % 8 || g.vps % 8 || g.ops % 8) return false;
-  for (int i = 0; i < 7; ++i)
-    if (ps[i] && ((uintptr_t)ps[i] & 15)) return false;
-  return true;
+// the MFMA kernels: bf16, head dim 32 / 64 / 128, every token stride and base a whole 16-byte vector (null passes)
+inline bool mfma_ok(int dtype, const MhaGeom& g, std::initializer_list<const void*> ps) {
+  if (dtype != 1 || !(g.d == 32 || g.d == 64 || g.d == 128)) return false;
+  return vec_ok(8, g.d, {g.qps, g.kps, g.vps, g.ops}, {}, ps);
+}
+// f(Int<32 / 64 / 128>) for the head dim of an MFMA launch
+template <int N> using Int = std::integral_constant<int, N>;
+template <typename F> inline int by_head_dim(int d, F&& f) {
+  return d == 32 ? f(Int<32>{}) : d == 64 ? f(Int<64>{}) : f(Int<128>{});
+}
+// the generic forward (any head dim <= 128, either dtype): dmy_mha_fwd's scalar path and dmy_mha_fwd_ref
+inline int mha_fwd_any(int dtype, const void* q, const void* k, const void* v, void* o, float* lse2, const MhaGeom& g,
+                       void* stream) {
+  return by_dtype(dtype, kInvalid, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    return launch(mha_fwd_generic<T>, dim3(ceil_div(g.L, 64), g.nh, g.B), 64, 0, stream, q, k, v, o, lse2, g);
+  });
 }
 
 }  // namespace
 
 // ================================================================ C ABI (include/dmayolo.h)
+// A dtype other than 0 (fp32) or 1 (bf16) is refused with hipErrorInvalidValue before anything else is looked at.
 DMY_API int dmy_mha_fwd(int dtype, const void* q, long qps, const void* k, long kps, const void* v, long vps, void* o,
                         long ops, float* lse2, int B, int L, int nh, int d, float scale, void* stream) {
-  hipStream_t st = (hipStream_t)stream;
+  if (dtype != 0 && dtype != 1) return kInvalid;
   if (B <= 0 || L <= 0) return 0;
-  if (d <= 0 || d > 128 || nh <= 0) return (int)hipErrorInvalidValue;
-  MhaGeom g{B, L, nh, d, qps, kps, vps, ops, scale};
-  const void* ps[7] = {q, k, v, o, nullptr, nullptr, nullptr};
-  if (mfma_ok(dtype, g, ps)) {
-    const dim3 grid(ceil_div(L, 128), nh, B);
-    const bf16 *Q = (const bf16*)q, *K = (const bf16*)k, *V = (const bf16*)v;
-    if (d == 32) mha_fwd_mfma<32><<<grid, 256, 0, st>>>(Q, K, V, (bf16*)o, lse2, g);
-    else if (d == 64) mha_fwd_mfma<64><<<grid, 256, 0, st>>>(Q, K, V, (bf16*)o, lse2, g);
-    else mha_fwd_mfma<128><<<grid, 256, 0, st>>>(Q, K, V, (bf16*)o, lse2, g);
-    return (int)hipGetLastError();
-  }
-  const dim3 grid(ceil_div(L, 64), nh, B);
-  if (dtype) mha_fwd_generic<bf16><<<grid, 64, 0, st>>>((const bf16*)q, (const bf16*)k, (const bf16*)v, (bf16*)o, lse2, g);
-  else mha_fwd_generic<float><<<grid, 64, 0, st>>>((const float*)q, (const float*)k, (const float*)v, (float*)o, lse2, g);
-  return (int)hipGetLastError();
+  if (d <= 0 || d > 128 || nh <= 0) return kInvalid;
+  const MhaGeom g{B, L, nh, d, qps, kps, vps, ops, scale};
+  if (!mfma_ok(dtype, g, {q, k, v, o})) return mha_fwd_any(dtype, q, k, v, o, lse2, g, stream);
+  return by_head_dim(d, [&](auto D) {
+    return launch(mha_fwd_mfma<D.value>, dim3(ceil_div(L, 128), nh, B), stream, q, k, v, o, lse2, g);
+  });
 }
 
 // dq / dk / dv use token stride `ops` (the stride of o / dO); Dq = fp32 workspace [B * nh * L]
 DMY_API int dmy_mha_bwd(int dtype, const void* q, long qps, const void* k, long kps, const void* v, long vps,
                         const void* o, const void* dout, long ops, const float* lse2, float* Dq, void* dq, void* dk,
                         void* dv, int B, int L, int nh, int d, float scale, void* stream) {
-  hipStream_t st = (hipStream_t)stream;
-  if (B <= 0 || L <= 0) return 0;
-  if (d <= 0 || d > 128 || nh <= 0) return (int)hipErrorInvalidValue;
-  MhaGeom g{B, L, nh, d, qps, kps, vps, ops, scale};
-  const int rg = grid_cap(ceil_div((long)B * L * nh, 256), 4096);
-  if (dtype) mha_rowdot<bf16><<<rg, 256, 0, st>>>((const bf16*)o, (const bf16*)dout, Dq, g);
-  else mha_rowdot<float><<<rg, 256, 0, st>>>((const float*)o, (const float*)dout, Dq, g);
-  const void* ps[7] = {q, k, v, dout, dq, dk, dv};
-  if (mfma_ok(dtype, g, ps)) {
-    const dim3 grid(ceil_div(L, 128), nh, B);
-    const bf16 *Q = (const bf16*)q, *K = (const bf16*)k, *V = (const bf16*)v, *DO = (const bf16*)dout;
-#define MHA_BWD(D)                                                                                      \
-    mha_bwd_dq_mfma<D><<<grid, 256, 0, st>>>(Q, K, V, DO, lse2, Dq, (bf16*)dq, g);                         \
-    mha_bwd_dkdv_mfma<D><<<grid, 256, 0, st>>>(Q, K, V, DO, lse2, Dq, (bf16*)dk, (bf16*)dv, g);
-    if (d == 32) { MHA_BWD(32) }
-    else if (d == 64) { MHA_BWD(64) }
-    else { MHA_BWD(128) }
-#undef MHA_BWD
-    return (int)hipGetLastError();
-  }
-  const dim3 g1(ceil_div(L, 64), nh, B), g2(ceil_div(L, 32), nh, B);
-  if (dtype) {
-    mha_bwd_dq_generic<bf16><<<g1, 64, 0, st>>>((const bf16*)q, (const bf16*)k, (const bf16*)v, (const bf16*)dout, lse2, Dq, (bf16*)dq, g);
-    mha_bwd_dkdv_generic<bf16><<<g2, 32, 0, st>>>((const bf16*)q, (const bf16*)k, (const bf16*)v, (const bf16*)dout, lse2, Dq, (bf16*)dk, (bf16*)dv, g);
-  } else {
-    mha_bwd_dq_generic<float><<<g1, 64, 0, st>>>((const float*)q, (const float*)k, (const float*)v, (const float*)dout, lse2, Dq, (float*)dq, g);
-    mha_bwd_dkdv_generic<float><<<g2, 32, 0, st>>>((const float*)q, (const float*)k, (const float*)v, (const float*)dout, lse2, Dq, (float*)dk, (float*)dv, g);
-  }
-  return (int)hipGetLastError();
+  return by_dtype(dtype, kInvalid, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    if (B <= 0 || L <= 0) return 0;
+    if (d <= 0 || d > 128 || nh <= 0) return kInvalid;
+    const MhaGeom g{B, L, nh, d, qps, kps, vps, ops, scale};
+    int rc = launch(mha_rowdot<T>, grid_cap(ceil_div((long)B * L * nh, 256), 4096), stream, o, dout, Dq, g);
+    if (rc != 0) return rc;
+    if (mfma_ok(dtype, g, {q, k, v, dout, dq, dk, dv})) {
+      const dim3 grid(ceil_div(L, 128), nh, B);
+      return by_head_dim(d, [&](auto D) {
+        rc = launch(mha_bwd_dq_mfma<D.value>, grid, stream, q, k, v, dout, lse2, Dq, dq, g);
+        return rc ? rc : launch(mha_bwd_dkdv_mfma<D.value>, grid, stream, q, k, v, dout, lse2, Dq, dk, dv, g);
+      });
+    }
+    rc = launch(mha_bwd_dq_generic<T>, dim3(ceil_div(L, 64), nh, B), 64, 0, stream, q, k, v, dout, lse2, Dq, dq, g);
+    if (rc != 0) return rc;
+    return launch(mha_bwd_dkdv_generic<T>, dim3(ceil_div(L, 32), nh, B), 32, 0, stream, q, k, v, dout, lse2, Dq, dk, dv,
+                  g);
+  });
 }
 
 // generic-path forward / backward regardless of dtype and head dim (test reference for the MFMA path)
 DMY_API int dmy_mha_fwd_ref(int dtype, const void* q, long qps, const void* k, long kps, const void* v, long vps,
                             void* o, long ops, float* lse2, int B, int L, int nh, int d, float scale, void* stream) {
-  hipStream_t st = (hipStream_t)stream;
+  if (dtype != 0 && dtype != 1) return kInvalid;
   if (B <= 0 || L <= 0) return 0;
-  if (d <= 0 || d > 128 || nh <= 0) return (int)hipErrorInvalidValue;
-  MhaGeom g{B, L, nh, d, qps, kps, vps, ops, scale};
-  const dim3 grid(ceil_div(L, 64), nh, B);
-  if (dtype) mha_fwd_generic<bf16><<<grid, 64, 0, st>>>((const bf16*)q, (const bf16*)k, (const bf16*)v, (bf16*)o, lse2, g);
-  else mha_fwd_generic<float><<<grid, 64, 0, st>>>((const float*)q, (const float*)k, (const float*)v, (float*)o, lse2, g);
-  return (int)hipGetLastError();
+  if (d <= 0 || d > 128 || nh <= 0) return kInvalid;
+  return mha_fwd_any(dtype, q, k, v, o, lse2, MhaGeom{B, L, nh, d, qps, kps, vps, ops, scale}, stream);
 }
 
 // seed = state = splitmix64 step of the per-device generator state (one lane, vector store): launched on the
@@ -714,11 +703,10 @@ DMY_API int dmy_dropout_seed(unsigned long long* state, unsigned long long* seed
 
 DMY_API int dmy_dropout(int dtype, const void* x, long xps, void* y, long yps, long M, int C, float p,
                         const unsigned long long* seed, void* stream) {
-  hipStream_t st = (hipStream_t)stream;
-  if (M * C == 0) return 0;
-  if (!(p >= 0.f && p < 1.f)) return (int)hipErrorInvalidValue;
-  const int g = grid_cap(ceil_div(M * C, 256), 8192);
-  if (dtype) dropout_kernel<bf16><<<g, 256, 0, st>>>((const bf16*)x, xps, (bf16*)y, yps, M, C, p, seed);
-  else dropout_kernel<float><<<g, 256, 0, st>>>((const float*)x, xps, (float*)y, yps, M, C, p, seed);
-  return (int)hipGetLastError();
+  return by_dtype(dtype, kInvalid, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    if (M * C == 0) return 0;
+    if (!(p >= 0.f && p < 1.f)) return kInvalid;
+    return launch(dropout_kernel<T>, grid_cap(ceil_div(M * C, 256), 8192), stream, x, xps, y, yps, M, C, p, seed);
+  });
 }

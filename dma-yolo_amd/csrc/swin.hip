@@ -12,7 +12,7 @@
 // One workgroup per (window, head); head_dim 32, window 8 (64 tokens); fp32 math in LDS.
 // Backward recomputes P (flash-style: nothing N x N is stored) and accumulates the
 // relative-position-bias gradient per workgroup in LDS, then once per workgroup to a slab.
-#include "common.h"
+#include "launch.h"
 
 namespace {
 
@@ -272,7 +272,7 @@ __global__ void __launch_bounds__(256) ln_bwd_vec(const T* __restrict__ x, long 
 // L = lanes per row (pow2 >= C / VW); 0 if the vector kernels do not apply
 template <typename T> int ln_lanes(int C, long xps, long yps, const void* x, const void* y) {
   constexpr int VW = Traits<T>::VW;
-  if (C % VW || xps % VW || yps % VW || (((uintptr_t)x | (uintptr_t)y) & 15)) return 0;
+  if (!vec_ok(VW, C, {xps, yps}, {}, {x, y})) return 0;
   const int n = C / VW;
   int L = 4;
   while (L < n) L <<= 1;
@@ -937,8 +937,10 @@ int ln_fwd_t(const T* x, long xps, const float* w, const float* b, T* y, float* 
 
 DMY_API int dmy_layernorm_fwd(int dtype, const void* x, long xps, const float* w, const float* b, void* y, float* mean,
                               float* rstd, long M, int C, float eps, void* stream) {
-  if (dtype) return ln_fwd_t<bf16>((const bf16*)x, xps, w, b, (bf16*)y, mean, rstd, M, C, eps, (hipStream_t)stream);
-  return ln_fwd_t<float>((const float*)x, xps, w, b, (float*)y, mean, rstd, M, C, eps, (hipStream_t)stream);
+  return by_dtype(dtype, kInvalid, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    return ln_fwd_t<T>((const T*)x, xps, w, b, (T*)y, mean, rstd, M, C, eps, (hipStream_t)stream);
+  });
 }
 
 DMY_API int dmy_layernorm_bwd_blocks(long M) { return grid_cap(ceil_div(M, 64), 1024); }
@@ -949,7 +951,7 @@ int ln_bwd_t(const T* x, long xps, const T* dy, long dps, const float* w, const 
   const int P = dmy_layernorm_bwd_blocks(M);
   const size_t lds = 4 * 2 * sizeof(float) * C;  // [4 waves][2][C]
   int L = ln_lanes<T>(C, xps, dxps, x, dx);
-  if (L && (dps % Traits<T>::VW || ((uintptr_t)dy & 15))) L = 0;
+  if (L && !vec_ok(Traits<T>::VW, C, {dps}, {}, {dy})) L = 0;
   switch (L) {
     case 4: ln_bwd_vec<T, 4><<<P, 256, lds, st>>>(x, xps, dy, dps, w, mean, rstd, dx, dxps, acc, M, C, pdw, pdb); break;
     case 8: ln_bwd_vec<T, 8><<<P, 256, lds, st>>>(x, xps, dy, dps, w, mean, rstd, dx, dxps, acc, M, C, pdw, pdb); break;
@@ -967,28 +969,28 @@ int ln_bwd_t(const T* x, long xps, const T* dy, long dps, const float* w, const 
 DMY_API int dmy_layernorm_bwd(int dtype, const void* x, long xps, const void* dy, long dps, const float* w,
                               const float* mean, const float* rstd, void* dx, long dxps, int accumulate, long M, int C,
                               float* pdw, float* pdb, void* stream) {
-  if (dtype)
-    return ln_bwd_t<bf16>((const bf16*)x, xps, (const bf16*)dy, dps, w, mean, rstd, (bf16*)dx, dxps, accumulate, M, C,
-                          pdw, pdb, (hipStream_t)stream);
-  return ln_bwd_t<float>((const float*)x, xps, (const float*)dy, dps, w, mean, rstd, (float*)dx, dxps, accumulate, M,
-                         C, pdw, pdb, (hipStream_t)stream);
+  return by_dtype(dtype, kInvalid, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    return ln_bwd_t<T>((const T*)x, xps, (const T*)dy, dps, w, mean, rstd, (T*)dx, dxps, accumulate, M, C, pdw, pdb,
+                       (hipStream_t)stream);
+  });
 }
 
 DMY_API int dmy_winattn_fwd(int dtype, const void* qkv, const float* table, void* out, int B, int H, int W, int C,
                             int nh, int shift, float scale, void* stream) {
-  if (C != nh * HD) return (int)hipErrorInvalidValue;
+  if (dtype != 0 && dtype != 1) return kInvalid;
+  if (C != nh * HD) return kInvalid;
   SwinGeom g = make(B, H, W, C, nh, shift, scale);
   const int nwin = B * (g.Rp / WS) * (g.Cp / WS);
-  dim3 grid(nwin, nh);
-  if (dtype) {
+  if (dtype) {  // bf16: the MFMA kernel; fp32: the scalar one
     constexpr int NW = 2;
     long groups = 4096 / (nh > 0 ? nh : 1);  // ~4096 blocks: every window group keeps a prefetch chain of a few windows
     if (groups > ceil_div(nwin, NW)) groups = ceil_div(nwin, NW);
     const int wpb = ceil_div(nwin, groups);
     const int g8 = ceil_div(ceil_div(nwin, wpb), 8) * 8;  // xgroup / xhead order
-    winattn_fwd_mfma<NW><<<g8 * nh, 64 * NW, 0, (hipStream_t)stream>>>((const bf16*)qkv, table, (bf16*)out, g, nwin, wpb);
-  } else winattn_fwd_kernel<float><<<grid, 256, 0, (hipStream_t)stream>>>((const float*)qkv, table, (float*)out, g);
-  return (int)hipGetLastError();
+    return launch(winattn_fwd_mfma<NW>, g8 * nh, 64 * NW, 0, stream, qkv, table, out, g, nwin, wpb);
+  }
+  return launch(winattn_fwd_kernel<float>, dim3(nwin, nh), stream, qkv, table, out, g);
 }
 
 DMY_API int dmy_winattn_bwd_groups(int B, int H, int W, int nh) {
@@ -1003,42 +1005,44 @@ DMY_API int dmy_winattn_bwd_groups(int B, int H, int W, int nh) {
 DMY_API int dmy_winattn_bwd(int dtype, const void* qkv, const void* dout, const float* table, void* dqkv,
                             float* dtab_part, float* dtab, int B, int H, int W, int C, int nh, int shift, float scale,
                             void* stream) {
-  if (C != nh * HD) return (int)hipErrorInvalidValue;
+  if (dtype != 0 && dtype != 1) return kInvalid;
+  if (C != nh * HD) return kInvalid;
   SwinGeom g = make(B, H, W, C, nh, shift, scale);
   const int nwin = B * (g.Rp / WS) * (g.Cp / WS);
   const int groups = dmy_winattn_bwd_groups(B, H, W, nh);
   const int wpb = (nwin + groups - 1) / groups;
-  dim3 grid(groups, nh);
-  hipStream_t st = (hipStream_t)stream;
-  if (dtype) winattn_bwd_mfma<2><<<groups * nh, 128, 0, st>>>((const bf16*)qkv, (const bf16*)dout, table, (bf16*)dqkv, dtab_part, nwin, wpb, g);
-  else winattn_bwd_kernel<float><<<grid, 256, 0, st>>>((const float*)qkv, (const float*)dout, table, (float*)dqkv, dtab_part, nwin, wpb, g);
-  const int ntab = (2 * WS - 1) * (2 * WS - 1) * nh;
-  dtab_reduce_kernel<<<ntab, 256, 0, st>>>(dtab_part, groups, nh, dtab);
-  return (int)hipGetLastError();
+  const int rc = dtype ? launch(winattn_bwd_mfma<2>, groups * nh, 128, 0, stream, qkv, dout, table, dqkv, dtab_part, nwin,
+                                wpb, g)
+                       : launch(winattn_bwd_kernel<float>, dim3(groups, nh), stream, qkv, dout, table, dqkv, dtab_part,
+                                nwin, wpb, g);
+  if (rc != 0) return rc;
+  return launch(dtab_reduce_kernel, (2 * WS - 1) * (2 * WS - 1) * nh, stream, dtab_part, groups, nh, dtab);
 }
 
 DMY_API int dmy_droppath_add(int dtype, const void* x, const void* f, const float* u, float keep, void* y, long per,
                              long n, void* stream) {
-  if (n == 0) return 0;
-  const int vec = dtype && per % 8 == 0 && (((uintptr_t)x | (uintptr_t)f | (uintptr_t)y) & 15) == 0;
-  const int g = grid_cap(ceil_div(vec ? n / 8 : n, 256), 16384);
-  if (dtype) droppath_add_kernel<bf16><<<g, 256, 0, (hipStream_t)stream>>>((const bf16*)x, (const bf16*)f, u, keep, (bf16*)y, per, n, vec);
-  else droppath_add_kernel<float><<<g, 256, 0, (hipStream_t)stream>>>((const float*)x, (const float*)f, u, keep, (float*)y, per, n, 0);
-  return (int)hipGetLastError();
+  return by_dtype(dtype, kInvalid, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    if (n == 0) return 0;
+    const int vec = dtype && vec_ok(8, 0, {per}, {}, {x, f, y});  // bf16 only; fp32 runs the scalar form
+    return launch(droppath_add_kernel<T>, grid_cap(ceil_div(vec ? n / 8 : n, 256), 16384), stream, x, f, u, keep, y, per,
+                  n, vec);
+  });
 }
 DMY_API int dmy_droppath_grad(int dtype, const void* dy, const float* u, float keep, void* df, long per, long n,
                               void* stream) {
-  if (n == 0) return 0;
-  const int vec = dtype && per % 8 == 0 && (((uintptr_t)dy | (uintptr_t)df) & 15) == 0;
-  const int g = grid_cap(ceil_div(vec ? n / 8 : n, 256), 16384);
-  if (dtype) droppath_grad_kernel<bf16><<<g, 256, 0, (hipStream_t)stream>>>((const bf16*)dy, u, keep, (bf16*)df, per, n, vec);
-  else droppath_grad_kernel<float><<<g, 256, 0, (hipStream_t)stream>>>((const float*)dy, u, keep, (float*)df, per, n, 0);
-  return (int)hipGetLastError();
+  return by_dtype(dtype, kInvalid, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    if (n == 0) return 0;
+    const int vec = dtype && vec_ok(8, 0, {per}, {}, {dy, df});
+    return launch(droppath_grad_kernel<T>, grid_cap(ceil_div(vec ? n / 8 : n, 256), 16384), stream, dy, u, keep, df, per,
+                  n, vec);
+  });
 }
 
 DMY_API int dmy_sample_scale(int dtype, const void* x, const float* sc, void* y, long per, long n, void* stream) {
-  const int g = grid_cap(ceil_div(n, 256), 8192);
-  if (dtype) sample_scale_kernel<bf16><<<g, 256, 0, (hipStream_t)stream>>>((const bf16*)x, sc, (bf16*)y, per, n);
-  else sample_scale_kernel<float><<<g, 256, 0, (hipStream_t)stream>>>((const float*)x, sc, (float*)y, per, n);
-  return (int)hipGetLastError();
+  return by_dtype(dtype, kInvalid, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    return launch(sample_scale_kernel<T>, grid_cap(ceil_div(n, 256), 8192), stream, x, sc, y, per, n);
+  });
 }

@@ -20,7 +20,7 @@
 //   cls: BCEWithLogits(cls, t, pos_weight) with t = norm on the assigned label, box: (1 - CIoU)*norm,
 //   dfl: per side CE(bins, floor(t)) * (floor(t) + 1 - t) + CE(bins, floor(t) + 1) * (t - floor(t)),
 //   mean over sides, * norm;  loss = (7.5 box + 0.5 cls + 1.5 dfl) * B.
-#include "common.h"
+#include "launch.h"
 #include "dual.h"
 
 namespace {
@@ -474,15 +474,6 @@ inline int egrid(long n) { return grid_cap(ceil_div(n, 256), 8192); }
 
 }  // namespace
 
-#define TAL_T(dtype, ...)    \
-  if (dtype) {               \
-    using T = bf16;          \
-    __VA_ARGS__;             \
-  } else {                   \
-    using T = float;         \
-    __VA_ARGS__;             \
-  }
-
 DMY_API long dmy_tal_workspace_bytes(int B, int A, int cap) {
   // gt[B][cap][5] f32, cnt[B] i32, cand[B][cap][10] i32, nclaim/owner [B][A] i32, metric/norm [B][A] f32,
   // amax_m/amax_o [B][cap] i32, pbox [B][A][4] f32, acc[4] f32, per-block loss partials [8192][4] f32
@@ -498,7 +489,8 @@ DMY_API int dmy_tal_loss(int dtype, const void* box, long sbb, long sbc, long sb
                          const float* targets, int nt, float alpha, float beta, float pos_weight, void* workspace,
                          float* G, float* loss, float* items, void* stream) {
   hipStream_t st = (hipStream_t)stream;
-  if (nl < 1 || nl > 8) return (int)hipErrorInvalidValue;
+  if (dtype != 0 && dtype != 1) return kInvalid;
+  if (nl < 1 || nl > 8) return kInvalid;
   LevelTab lt = make_levels(nl, H, W, stride);
   const int A = lt.a0[nl];
   const int cap = nt > 0 ? nt : 1;
@@ -524,7 +516,9 @@ DMY_API int dmy_tal_loss(int dtype, const void* box, long sbb, long sbc, long sb
   const float iw = (float)W[0] * stride[0], ih = (float)H[0] * stride[0];
   if (nt > 0) tal_targets_kernel<<<1, 256, 0, st>>>(targets, nt, B, iw, ih, cap, gt, cnt);
   else (void)hipMemsetAsync(cnt, 0, 4L * B, st);
-  TAL_T(dtype, {
+  // one status for the chain, as before: the last error of the launches
+  return by_dtype(dtype, kInvalid, [&](auto tag) {
+    using T = typename decltype(tag)::type;
     const T* bx = (const T*)box;
     const T* cl = (const T*)cls;
     tal_decode_kernel<T><<<egrid((long)B * A), 256, 0, st>>>(bx, sbb, sbc, sba, B, A, lt, pbox);
@@ -539,25 +533,26 @@ DMY_API int dmy_tal_loss(int dtype, const void* box, long sbb, long sbc, long sb
     tal_loss_kernel<T><<<nb, 256, 0, st>>>(bx, sbb, sbc, sba, cl, scb, scc, sca, gt, owner, norm, B, A, nc, cap, lt,
                                            pos_weight, acc, part, G);
     tal_fold_kernel<3><<<1, 256, 0, st>>>(part, nb, acc, 0);
+    tal_finalize_kernel<<<1, 1, 0, st>>>(acc, (float)B, loss, items);
+    return (int)hipGetLastError();
   });
-  tal_finalize_kernel<<<1, 1, 0, st>>>(acc, (float)B, loss, items);
-  return (int)hipGetLastError();
 }
 
 DMY_API int dmy_tal_flatten(int dtype, const void* x, long xps, int B, int H, int W, int A, int a0, int no, void* F,
                             int backward, void* stream) {
-  hipStream_t st = (hipStream_t)stream;
-  TAL_T(dtype, tal_flatten_kernel<T><<<egrid((long)B * H * W * no), 256, 0, st>>>((const T*)x, xps, B, H * W, A, a0, no,
-                                                                                   (T*)F, backward));
-  return (int)hipGetLastError();
+  return by_dtype(dtype, kInvalid, [&](auto tag) {
+    return launch(tal_flatten_kernel<typename decltype(tag)::type>, egrid((long)B * H * W * no), stream, x, xps, B, H * W,
+                  A, a0, no, F, backward);
+  });
 }
 
 DMY_API int dmy_tal_detect_out(int dtype, const void* F, int B, int nc, int nl, const int* H, const int* W,
                                const float* stride, float* y, void* stream) {
-  hipStream_t st = (hipStream_t)stream;
-  if (nl < 1 || nl > 8) return (int)hipErrorInvalidValue;
+  if (dtype != 0 && dtype != 1) return kInvalid;
+  if (nl < 1 || nl > 8) return kInvalid;
   LevelTab lt = make_levels(nl, H, W, stride);
-  const int A = lt.a0[nl];
-  TAL_T(dtype, tal_detect_out_kernel<T><<<egrid((long)B * A), 256, 0, st>>>((const T*)F, B, A, nc, lt, y));
-  return (int)hipGetLastError();
+  return by_dtype(dtype, kInvalid, [&](auto tag) {
+    return launch(tal_detect_out_kernel<typename decltype(tag)::type>, egrid((long)B * lt.a0[nl]), stream, F, B, lt.a0[nl],
+                  nc, lt, y);
+  });
 }

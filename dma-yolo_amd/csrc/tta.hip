@@ -6,7 +6,7 @@
 // neighbouring output columns, so the four taps of a channel plane read (nearly) consecutive addresses across the
 // wave and every store is a 16-byte vector.  The flip is folded into the tap index; the image is normalised
 // (uint8 * scale) per tap, combined in fp32 and rounded once to T.
-#include "common.h"
+#include "launch.h"
 
 namespace {
 
@@ -78,15 +78,13 @@ __global__ void tta_image_kernel(const S* __restrict__ x, T* __restrict__ y, int
 }
 
 template <typename S, int P>
-int launch(int dtype, const void* x, void* y, int N, int C, int H, int W, int Cs, float scale, int flip, int OH, int OW,
-           int OHp, int OWp, float pad_value, hipStream_t st) {
+int tta_launch(int dtype, const void* x, void* y, int N, int C, int H, int W, int Cs, float scale, int flip, int OH,
+               int OW, int OHp, int OWp, float pad_value, void* stream) {
   const long n = (long)N * (OHp / P) * (OWp / P);
-  const int g = grid_cap(ceil_div(n, 256), 8192);
-  if (dtype)
-    tta_image_kernel<S, bf16, P><<<g, 256, 0, st>>>((const S*)x, (bf16*)y, N, C, H, W, Cs, scale, flip, OH, OW, OHp, OWp, pad_value);
-  else
-    tta_image_kernel<S, float, P><<<g, 256, 0, st>>>((const S*)x, (float*)y, N, C, H, W, Cs, scale, flip, OH, OW, OHp, OWp, pad_value);
-  return (int)hipGetLastError();
+  return by_dtype(dtype, kInvalid, [&](auto tag) {
+    return launch(tta_image_kernel<S, typename decltype(tag)::type, P>, grid_cap(ceil_div(n, 256), 8192), stream, x, y,
+                  N, C, H, W, Cs, scale, flip, OH, OW, OHp, OWp, pad_value);
+  });
 }
 
 }  // namespace
@@ -96,15 +94,15 @@ int launch(int dtype, const void* x, void* y, int N, int C, int H, int W, int Cs
 // 3 left-right.  Pixels outside OH x OW hold pad_value, channels past the image's hold zero.
 DMY_API int dmy_tta_image(int dtype, int src_kind, const void* x, void* y, int N, int C, int H, int W, int s2d, int Cs,
                           float scale, int flip, int OH, int OW, int OHp, int OWp, float pad_value, void* stream) {
-  const int VW = dtype ? 8 : 4, P = s2d ? 2 : 1;
-  if (N < 1 || C < 1 || H < 1 || W < 1 || OH < 1 || OW < 1 || OH > OHp || OW > OWp) return (int)hipErrorInvalidValue;
-  if (flip != 0 && flip != 2 && flip != 3) return (int)hipErrorInvalidValue;
-  if (s2d && ((OHp | OWp) & 1)) return (int)hipErrorInvalidValue;
-  if (Cs % VW || Cs < P * P * C || (((uintptr_t)y) & 15)) return (int)hipErrorInvalidValue;
-  hipStream_t st = (hipStream_t)stream;
+  if (dtype != 0 && dtype != 1) return kInvalid;
+  const int P = s2d ? 2 : 1;
+  if (N < 1 || C < 1 || H < 1 || W < 1 || OH < 1 || OW < 1 || OH > OHp || OW > OWp) return kInvalid;
+  if (flip != 0 && flip != 2 && flip != 3) return kInvalid;
+  if (s2d && ((OHp | OWp) & 1)) return kInvalid;
+  if (!vec_ok(vec_width(dtype), Cs, {}, {}, {y}) || Cs < P * P * C) return kInvalid;
   if (src_kind == 0)
-    return s2d ? launch<uint8_t, 2>(dtype, x, y, N, C, H, W, Cs, scale, flip, OH, OW, OHp, OWp, pad_value, st)
-               : launch<uint8_t, 1>(dtype, x, y, N, C, H, W, Cs, scale, flip, OH, OW, OHp, OWp, pad_value, st);
-  return s2d ? launch<float, 2>(dtype, x, y, N, C, H, W, Cs, scale, flip, OH, OW, OHp, OWp, pad_value, st)
-             : launch<float, 1>(dtype, x, y, N, C, H, W, Cs, scale, flip, OH, OW, OHp, OWp, pad_value, st);
+    return s2d ? tta_launch<uint8_t, 2>(dtype, x, y, N, C, H, W, Cs, scale, flip, OH, OW, OHp, OWp, pad_value, stream)
+               : tta_launch<uint8_t, 1>(dtype, x, y, N, C, H, W, Cs, scale, flip, OH, OW, OHp, OWp, pad_value, stream);
+  return s2d ? tta_launch<float, 2>(dtype, x, y, N, C, H, W, Cs, scale, flip, OH, OW, OHp, OWp, pad_value, stream)
+             : tta_launch<float, 1>(dtype, x, y, N, C, H, W, Cs, scale, flip, OH, OW, OHp, OWp, pad_value, stream);
 }
