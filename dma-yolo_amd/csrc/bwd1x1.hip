@@ -13,7 +13,7 @@
 //   * Wt (the IHWO weight copy, [C][K]) is loaded into LDS once per block (16-B chunks XOR-swizzled by row).
 //   * Per tile: the (dy, z, x) loads of the NEXT tile are in flight in registers while this tile computes.  dz is
 //     computed by the thread that loaded it (its 8-channel chunk is fixed for the launch, so the BN / act coefficients
-//     stay in registers) and written with x into k-major LDS tiles ([pixel][channel], conv.hip's kmaj swizzle).
+//     stay in registers) and written with x into k-major LDS tiles ([pixel][channel], conv_core.h's kmaj swizzle).
 //   * Data-grad: D^T[c][px] = sum_k Wt[c][k] dz[px][k] (v_mfma_f32_16x16x32_bf16, W from LDS, dz row fragments from
 //     LDS), in units of 32 pixels x 64 channels per wave; a permlane16 swap gives each lane 8 consecutive channels of one
 //     pixel, so a pixel's 128-B line leaves in two back-to-back 16-B stores (the store order round 4 measured fastest).
@@ -41,7 +41,7 @@ DEV uint4 bload(__amdgpu_buffer_rsrc_t r, unsigned off) {
 }
 
 // k-major tile [k = pixel][ROW = channels], 16-B chunks XOR-swizzled per pixel row so the transposed reads of 8
-// consecutive pixels are bank-conflict free (the kmaj layout of conv.hip's weight-grad tiles)
+// consecutive pixels are bank-conflict free (the kmaj layout of conv_wgrad.hip's weight-grad tiles)
 template <int ROW> DEV int ksw(int k, int row) {
   constexpr int RB = ROW * 2;
   const int c = row >> 3, w = row & 7;

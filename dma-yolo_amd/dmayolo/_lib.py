@@ -21,25 +21,26 @@ P, I, L, F, D = ctypes.c_void_p, ctypes.c_int, ctypes.c_long, ctypes.c_float, ct
 # *_last_rows queries, else int (a hipError_t, a size for the *_rows / *_blocks / *_groups queries, or a KERN code
 # for dmy_conv_route)
 SIGNATURES = {
-    # conv.hip
+    # conv.hip (forward, data-grad, the route query of all three passes)
     'dmy_conv_fwd_partial_rows': [L, I],
     'dmy_conv_fwd_bound_rows': [L, I],
     'dmy_conv_fwd_last_rows': [],
     'dmy_conv_fwd_bn_rows': [I, P, P, P, P, I, I, I, I, L, I, I, I, I, I, I, I, L],
     'dmy_conv_fwd': [I, P, P, P, P, P, P, I, I, I, I, L, I, I, I, I, I, I, I, L, P],
     'dmy_conv_dgrad': [I, P, P, P, I, I, I, I, I, L, I, I, I, I, I, I, I, L, P],
+    'dmy_conv_fwd_act': [I, P, P, P, P, I, I, I, I, L, I, I, I, I, I, I, I, L, P, P, I, P, L, P],
+    'dmy_conv_fwd_splitk_elems': [I, P, P, P, I, I, I, I, L, I, I, I, I, I, I, I, L],
+    'dmy_conv_fwd_act_ws': [I, P, P, P, P, I, I, I, I, L, I, I, I, I, I, I, I, L, P, P, I, P, L, P, L, P],
+    'dmy_conv_route': [I, I, P, P, P, I, I, I, I, L, I, I, I, I, I, I, I, L, I],
+    # conv_wgrad.hip (weight-grad, weight prep; dmy_image_s2d, the image side of the s2d stem, is eltwise.hip's)
     'dmy_conv_wgrad': [I, P, P, P, I, I, I, I, L, I, I, I, I, I, I, I, L, P],
     'dmy_conv_wprep_multi': [I, P, I, P],
     'dmy_conv_wprep_s2d': [I, P, P, I, I, I, P],
     'dmy_conv_wgrad_s2d_to_oihw': [P, P, I, I, I, P],
     'dmy_image_s2d': [I, I, P, P, I, I, I, I, I, F, P],
-    'dmy_conv_fwd_act': [I, P, P, P, P, I, I, I, I, L, I, I, I, I, I, I, I, L, P, P, I, P, L, P],
-    'dmy_conv_fwd_splitk_elems': [I, P, P, P, I, I, I, I, L, I, I, I, I, I, I, I, L],
-    'dmy_conv_fwd_act_ws': [I, P, P, P, P, I, I, I, I, L, I, I, I, I, I, I, I, L, P, P, I, P, L, P, L, P],
     'dmy_conv_wgrad_ex': [I, P, P, P, I, I, I, I, L, I, I, I, I, I, I, I, L, I, P],
     'dmy_conv_wgrad_ws_elems': [I, P, P, I, I, I, I, L, I, I, I, I, I, I, I, L, I],
     'dmy_conv_wgrad_det': [I, P, P, P, I, I, I, I, L, I, I, I, I, I, I, I, L, I, P, L, P],
-    'dmy_conv_route': [I, I, P, P, P, I, I, I, I, L, I, I, I, I, I, I, I, L, I],
     'dmy_conv_wprep': [I, P, P, P, I, I, I, I, I, P],
     # dwconv.hip
     'dmy_dwconv_ok': [I, P, P, P, I, I, I, I, I, I, L, I, I, I, I, I, I, L],

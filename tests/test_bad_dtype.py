@@ -8,8 +8,10 @@ INVALID = 1  # hipErrorInvalidValue
 
 LAUNCH = [
     # conv.hip
-    'dmy_conv_fwd', 'dmy_conv_fwd_act', 'dmy_conv_fwd_act_ws', 'dmy_conv_dgrad', 'dmy_conv_wgrad', 'dmy_conv_wgrad_ex',
-    'dmy_conv_wgrad_det', 'dmy_conv_wprep', 'dmy_conv_wprep_multi', 'dmy_conv_wprep_s2d',
+    'dmy_conv_fwd', 'dmy_conv_fwd_act', 'dmy_conv_fwd_act_ws', 'dmy_conv_dgrad',
+    # conv_wgrad.hip
+    'dmy_conv_wgrad', 'dmy_conv_wgrad_ex', 'dmy_conv_wgrad_det', 'dmy_conv_wprep', 'dmy_conv_wprep_multi',
+    'dmy_conv_wprep_s2d',
     # mha.hip
     'dmy_mha_fwd', 'dmy_mha_fwd_ref', 'dmy_mha_bwd', 'dmy_dropout',
     # swin.hip

@@ -168,7 +168,8 @@ def _wide(M, gn, NC):
 
 def test_conv_routes():
     """dmy_conv_route (query only, no launch): one shape per data-grad and weight-grad kernel kind, the expected kind
-    worked out by hand from the routing rules of csrc/conv.hip (plan_dgrad / plan_v3 / plan_wgrad) with the device's
+    worked out by hand from the routing rules of csrc/conv.hip (plan_dgrad / plan_v3) and csrc/conv_wgrad.hip
+    (plan_wgrad) with the device's
     CU count NC; on 256 CUs every kind is reached.  Shapes are (N, C, H, W, K, k, s) from SHAPES, the tap list and the
     bench-shape lists where those reach the kind."""
     from dmayolo._lib import call, KERN, ROUTE_DGRAD, ROUTE_WGRAD
