@@ -182,6 +182,10 @@ SIGNATURES = {
     'dmy_nms_greedy': [P, I, I, I, F, I, I, I, P, L, P, P, P, P, P, P],
     'dmy_nms_mask_rows': [],
     'dmy_nms_greedy_mask': [P, I, I, I, F, I, I, I, P, L, P, P, P, P, P, P, P],
+    # wbf.hip
+    'dmy_wbf_max_rows': [],
+    'dmy_wbf_workspace_bytes': [I, I],
+    'dmy_wbf': [P, P, P, P, I, I, I, D, D, P, P, P, P],
     # metrics.hip
     'dmy_process_batch': [P, P, P, P, I, P, I, P, P, P, P, P],
     # swin.hip

@@ -1,6 +1,6 @@
 """Checkpoint files: the reference's ckpt dict (train.py:515-522) with the model /
-EMA entries stored as state_dicts, plus attempt_load (models/experimental.py:113-153) and intersect_dicts
-(utils/torch_utils.py:156-158).
+EMA entries stored as state_dicts, plus attempt_load (models/experimental.py:113-153) with its Ensemble
+(models/experimental.py:92-111) and intersect_dicts (utils/torch_utils.py:156-158).
 
 The reference pickles whole nn.Module objects ('model': deepcopy(de_parallel(model)).half()).  Loading
 such a file executes the pickled class references, so this build never reads one with a pickle-capable
@@ -12,6 +12,7 @@ reference .pt is converted once, on a machine that trusts it, with
 from datetime import datetime
 
 import torch
+import torch.nn as nn
 
 from ..models.yolo import Model
 
@@ -59,9 +60,29 @@ def load_weights(model, path_or_sd, exclude=(), key='model'):
     return len(csd)
 
 
+class Ensemble(nn.ModuleList):
+    """models/experimental.py:92-111: the members' decoded outputs concatenated along the anchor axis (the 'nms
+    ensemble': one NMS then sees every member's predictions); no per-level outputs."""
+
+    def forward(self, x, augment=False, profile=False, visualize=False):
+        y = [module(x, augment, profile, visualize)[0] for module in self]
+        return torch.cat(y, 1), None
+
+
 def attempt_load(path, device='cuda', fuse=True, act_dtype=torch.float32):
     """models/experimental.py:113-153 for one save_checkpoint file: rebuild the Model from the stored yaml,
-    load 'ema' if present else 'model' (fp32), fuse BN into the YAML Conv layers, eval mode."""
+    load 'ema' if present else 'model' (fp32), fuse BN into the YAML Conv layers, eval mode.  A list or tuple of
+    files gives an Ensemble of those models carrying the last member's `names` and the `stride` of the member with
+    the largest stride (experimental.py:141-153); a list of one file gives the bare Model."""
+    if isinstance(path, (list, tuple)):
+        model = Ensemble()
+        for p in path:
+            model.append(attempt_load(p, device, fuse, act_dtype))
+        if len(model) == 1:
+            return model[-1]
+        model.names = model[-1].names
+        model.stride = model[max(range(len(model)), key=lambda i: float(model[i].stride.max()))].stride
+        return model.eval()
     ckpt = torch.load(path, map_location='cpu', weights_only=True)
     model = Model(ckpt['yaml'], act_dtype=act_dtype)
     load_weights(model, ckpt, key='ema')  # ckpt['ema'] or ckpt['model'] (experimental.py:128)

@@ -8,13 +8,21 @@ gives P, R, mAP@0.5 and mAP@0.5:0.95 exactly as val.py:283-291.
 Batches are what dmayolo.data.create_dataloader yields (datasets.py:624-629's collate: uint8 images at the
 network size [N, 3, H, W], normalised targets [nt, 6] (img, cls, x, y, w, h), paths, shapes), or
 (img, targets[, shapes]) tensors; `shapes` (per-image (h0, w0), ((ratio), (pad))) drive scale_coords.
+
+Multi-model ensembles (the reference's val2.py per model -> txt -> wbf.py chain, wbf.py:33-67): run() takes a list of
+models plus wbf=dict(iou_thr, skip_box_thr, weights).  Each batch goes through every model and its own NMS, the padded
+NMS buffers are fused on the device by weighted boxes fusion over the network-size image (utils/wbf.wbf_padded), and the
+statistics are taken from the fused rows.
 Out of scope (control plane): plots, COCO-JSON, confusion matrix, txt saving.
 """
 import numpy as np
 import torch
 
-from .utils.general import non_max_suppression, scale_coords, xywh2xyxy
+from .utils.general import nms_padded, non_max_suppression, scale_coords, xywh2xyxy
 from .utils.metrics import ap_per_class, process_batch_multi
+from .utils.wbf import wbf_padded
+
+WBF_DEFAULTS = dict(iou_thr=0.67, skip_box_thr=0.01, weights=None)  # wbf.py:33-34
 
 
 def batch_stats(out, targets, img_hw, iouv, shapes=None, single_cls=False):
@@ -74,16 +82,54 @@ def summarize(stats, nc):
     return mp, mr, map50, map_, maps, nt
 
 
+def fused_detections(outs, img_hw, conf_thres, iou_thres, max_det, single_cls, wbf):
+    """the ensemble's post-process for one batch: outs = each model's decoded output -> per model nms_padded, then one
+    weighted boxes fusion over the (height, width) network image; returns the per-image fused [k, 6] rows"""
+    height, width = img_hw
+    bufs, counts = [], []
+    for out in outs:
+        buf, res = nms_padded(out, conf_thres, iou_thres, multi_label=True, agnostic=single_cls, max_det=max_det)
+        bufs.append(buf)
+        counts.append([len(r) for r in res])
+    nimg = len(counts[0])
+    if nimg == 0:
+        return []
+    dev = bufs[0].device
+    wh = torch.tensor([[width, height]] * nimg, dtype=torch.float32, device=dev)
+    return wbf_padded(torch.stack(bufs), torch.tensor(counts, dtype=torch.int32, device=dev), wh, wbf['weights'],
+                      wbf['iou_thr'], wbf['skip_box_thr'])[1]
+
+
 @torch.no_grad()
 def run(model, batches, nc, conf_thres=0.001, iou_thres=0.6, max_det=300, single_cls=False, compute_loss=None,
-        augment=False):
+        augment=False, wbf=None):
     """Returns ((mp, mr, map50, map, *loss), maps [nc], seen, nt [nc]) like val.py:303-311.  augment: the model's
-    test-time-augmented forward (val.py:213); it has no per-level outputs, so it excludes compute_loss."""
+    test-time-augmented forward (val.py:213); it has no per-level outputs, so it excludes compute_loss.
+    model may be a list or tuple of models with wbf=dict(iou_thr=0.67, skip_box_thr=0.01, weights=None) (missing
+    entries take these defaults, wbf.py:33-34): every batch goes through each model and its own NMS, and weighted
+    boxes fusion over the network-size image makes the rows the statistics see.  The fused path has no per-level
+    outputs either, so it excludes compute_loss."""
     if augment and compute_loss:
         raise ValueError('augment=True returns no per-level outputs for compute_loss (val.py:213-217)')
-    device = next(model.parameters()).device
-    was_training = model.training
-    model.eval()
+    many = isinstance(model, (list, tuple))
+    if many and wbf is None:
+        raise ValueError('a list of models needs wbf=dict(...): their detections are fused, not concatenated')
+    if wbf is not None and compute_loss:
+        raise ValueError('wbf fuses detections of several forwards: there are no per-level outputs for compute_loss')
+    if wbf is not None:
+        unknown = set(wbf) - set(WBF_DEFAULTS)
+        if unknown:
+            raise ValueError(f'unknown wbf entries {sorted(unknown)}')
+        wbf = {**WBF_DEFAULTS, **wbf}
+        models = list(model) if many else [model]
+        if not models:
+            raise ValueError('an empty list of models')
+    else:
+        models = [model]
+    device = next(models[0].parameters()).device
+    was_training = [m.training for m in models]
+    for m in models:
+        m.eval()
     iouv = torch.linspace(0.5, 0.95, 10, device=device)  # val.py:163
     seen = nbatches = 0
     loss = torch.zeros(3, device=device)
@@ -94,15 +140,23 @@ def run(model, batches, nc, conf_thres=0.001, iou_thres=0.6, max_det=300, single
         img = img.to(device, non_blocking=True)
         targets = targets.to(device).float()
         nb, _, height, width = img.shape
-        out, train_out = model(img, augment=True) if augment else model(img)
+        if wbf is not None:
+            outs = [(m(img, augment=True) if augment else m(img))[0] for m in models]
+        else:
+            out, train_out = model(img, augment=True) if augment else model(img)
         if compute_loss:
             loss += compute_loss([x.float() for x in train_out], targets)[1]
         targets[:, 2:] *= torch.tensor([width, height, width, height], device=device, dtype=torch.float32)
-        out = non_max_suppression(out, conf_thres, iou_thres, multi_label=True, agnostic=single_cls, max_det=max_det)
+        if wbf is not None:
+            out = fused_detections(outs, (height, width), conf_thres, iou_thres, max_det, single_cls, wbf)
+        else:
+            out = non_max_suppression(out, conf_thres, iou_thres, multi_label=True, agnostic=single_cls,
+                                      max_det=max_det)
         nbatches += 1
         seen += len(out)
         stats += batch_stats(out, targets, (height, width), iouv, shapes, single_cls)
     mp, mr, map50, map_, maps, nt = summarize(stats, nc)
-    model.train(was_training)
+    for m, t in zip(models, was_training):
+        m.train(t)
     loss_items = (loss.cpu() / max(nbatches, 1)).tolist()
     return (mp, mr, map50, map_, *loss_items), maps, seen, nt

@@ -639,6 +639,20 @@ int dmy_letterbox_batch(int dtype, const void* descs, const void* host_descs, in
 int dmy_scale_boxes(void* det, const void* counts, const void* geom, void* xywh, void* xyxyn, void* xywhn, int nimg,
                     int max_det, void* stream);
 
+/* ---- weighted boxes fusion (wbf.hip): ensemble_boxes.weighted_boxes_fusion, conf_type 'avg', allows_overflow False,
+ *      as the reference's multi-model evaluation calls it (wbf.py:67), for every image of a batch at once. */
+/* wbf.py:67 -- the most records (M * R) per image dmy_wbf takes */
+int dmy_wbf_max_rows(void);
+/* wbf.py:67 -- bytes of the workspace dmy_wbf needs for nimg images of rows = M * R records */
+long dmy_wbf_workspace_bytes(int nimg, int rows);
+/* wbf.py:67 -- det [M][nimg][R][6] fp32 (xyxy in pixels, conf, cls: the padded NMS layout stacked over M models),
+ * counts [M][nimg] int32 valid rows, wh [nimg][2] fp32 image (width, height), weights [M] fp64 -> out [nimg][M * R][6]
+ * fp32 fused rows (xyxy in pixels, score, label) in descending score order and nout [nimg] int32 row counts.  fp64
+ * arithmetic, one rounding per operation.  M * R above dmy_wbf_max_rows, nimg above 65535 or a null / misaligned
+ * pointer return hipErrorInvalidValue before any launch. */
+int dmy_wbf(const float* det, const int* counts, const float* wh, const double* weights, int M, int nimg, int R,
+            double iou_thr, double skip_box_thr, void* ws, float* out, int* nout, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
