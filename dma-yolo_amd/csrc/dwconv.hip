@@ -594,14 +594,23 @@ bool geom_ok(int dtype, int N, int H, int W, int C, long xps, int KH, int KW, in
   return true;
 }
 
-#define DW_K_S(KK, SS, ...)                      \
-  if (KH == KK && S == SS) {                     \
-    constexpr int K_ = KK, S_ = SS;              \
-    __VA_ARGS__;                                 \
-  }
-#define DW_DISPATCH35(...)                                                                            \
-  DW_K_S(3, 1, __VA_ARGS__) DW_K_S(3, 2, __VA_ARGS__) DW_K_S(5, 1, __VA_ARGS__) DW_K_S(5, 2, __VA_ARGS__)
-#define DW_DISPATCH(...) DW_DISPATCH35(__VA_ARGS__) DW_K_S(7, 1, __VA_ARGS__)  // k7 is stride 1 only (geom_ok); k9 has its own kernels
+// f(Width<K>{}, Width<S>{}) for the (K, S) pairs geom_ok admits (K = 7 / 9 are stride 1 only), -1 for any other.  f is a
+// generic lambda that holds the launch and returns the entry's int.
+template <typename F> int by_k_s(int K, int S, F&& f) {
+  if (K == 3 && S == 1) return f(Width<3>{}, Width<1>{});
+  if (K == 3 && S == 2) return f(Width<3>{}, Width<2>{});
+  if (K == 5 && S == 1) return f(Width<5>{}, Width<1>{});
+  if (K == 5 && S == 2) return f(Width<5>{}, Width<2>{});
+  if (K == 7 && S == 1) return f(Width<7>{}, Width<1>{});
+  if (K == 9 && S == 1) return f(Width<9>{}, Width<1>{});
+  return -1;
+}
+
+// the correlation kernel of (K, S): the 9 x 9 has a body of its own
+template <typename T, int K, int S, bool FLIP, int EPI> constexpr auto conv_kernel() {
+  if constexpr (K == 9) return &dw9_conv_kernel<T, FLIP, EPI>;
+  else return &dw_conv_kernel<T, K, S, FLIP, EPI>;
+}
 
 template <typename T, int EPI>
 int launch_fwd(const T* x, const T* w, const float* bias, T* y, float* psum, float* psq, int N, int H, int W, int C,
@@ -610,16 +619,15 @@ int launch_fwd(const T* x, const T* w, const float* bias, T* y, float* psum, flo
   constexpr int VW = Traits<T>::VW;
   const int tcl = tile_log2(C / VW);
   const dim3 grid = tile_grid(part_rows((long)N * OH * OW, kFwdRowCap), C / VW, tcl);
-  if (KH == 9) {
-    return launch(dw9_conv_kernel<T, false, EPI>, grid, st, x, w, bias, y, psum, psq, N, H, W, C, xps, OH, OW, yps, tcl,
-        scale, shift, act, res, rps, 0);
-  }
-  if constexpr (EPI != EPI_ACTBN) {  // the act-then-BN epilogue exists for the 9 x 9 only
-    DW_DISPATCH((dw_conv_kernel<T, K_, S_, false, EPI><<<grid, 256, 0, st>>>(x, w, bias, y, psum, psq, N, H, W, C, xps, OH,
-                                                                             OW, yps, tcl, scale, shift, act, res, rps, 0)))
-    return (int)hipGetLastError();
-  }
-  return -1;
+  return by_k_s(KH, S, [&](auto k, auto s) {
+    constexpr int K = decltype(k)::value, S_ = decltype(s)::value;
+    if constexpr (EPI == EPI_ACTBN && K != 9) {  // the act-then-BN epilogue exists for the 9 x 9 only
+      return -1;
+    } else {
+      return launch(conv_kernel<T, K, S_, false, EPI>(), grid, st, x, w, bias, y, psum, psq, N, H, W, C, xps, OH, OW, yps,
+                    tcl, scale, shift, act, res, rps, 0);
+    }
+  });
 }
 
 template <typename T>
@@ -628,40 +636,36 @@ int launch_dgrad(const T* dz, const T* w, T* dx, int accumulate, int N, int H, i
   constexpr int VW = Traits<T>::VW;
   const int tcl = tile_log2(C / VW);
   const dim3 grid = tile_grid(part_rows((long)N * H * W, kFwdRowCap), C / VW, tcl);
-  if (KH == 9) {
-    return launch(dw9_conv_kernel<T, true, EPI_ACC>, grid, st, dz, w, nullptr, dx, nullptr, nullptr, N, OH, OW, C, zps,
-        H, W, xps, tcl, nullptr, nullptr, 0, nullptr, 0, accumulate);
-  }
-  if (S == 1) {
-    // correlation of dz (OH x OW) with the flipped filter, same padding (P = K / 2, K odd), output H x W
-    DW_DISPATCH(if (S_ == 1) (dw_conv_kernel<T, K_, 1, true, EPI_ACC><<<grid, 256, 0, st>>>(
-        dz, w, nullptr, dx, nullptr, nullptr, N, OH, OW, C, zps, H, W, xps, tcl, nullptr, nullptr, 0, nullptr, 0, accumulate)))
-  } else {
-    DW_DISPATCH35(if (S_ == 2) (dw_dgrad_s2_kernel<T, K_><<<grid, 256, 0, st>>>(dz, w, dx, accumulate, N, H, W, C, xps, OH,
-                                                                                OW, zps, tcl)))
-  }
-  return (int)hipGetLastError();
+  return by_k_s(KH, S, [&](auto k, auto s) {
+    constexpr int K = decltype(k)::value, S_ = decltype(s)::value;
+    if constexpr (S_ == 1) {
+      // correlation of dz (OH x OW) with the flipped filter, same padding (P = K / 2, K odd), output H x W
+      return launch(conv_kernel<T, K, 1, true, EPI_ACC>(), grid, st, dz, w, nullptr, dx, nullptr, nullptr, N, OH, OW, C,
+                    zps, H, W, xps, tcl, nullptr, nullptr, 0, nullptr, 0, accumulate);
+    } else {
+      return launch(dw_dgrad_s2_kernel<T, K>, grid, st, dz, w, dx, accumulate, N, H, W, C, xps, OH, OW, zps, tcl);
+    }
+  });
 }
 
-// RL: floats between partial rows; bias: the rows also carry the bias gradient's share (the row-per-z kernel only)
+// RL: floats between partial rows; bias: the rows also carry the bias gradient's share (K = 7 only, checked by wgrad)
 template <typename T>
 int launch_wgrad(const T* x, const T* dz, float* part, long RL, int bias, int N, int H, int W, int C, long xps, int KH,
                  int S, int OH, int OW, long zps, hipStream_t st) {
   const int rows = part_rows((long)N * OH * OW, kWgRowCap);
-  if (KH == 9) {  // a 16-byte channel vector per thread, one filter row per blockIdx.z
-    if (bias) return -1;
-    const int t9 = tile_log2(C / Traits<T>::VW);
-    return launch(dw9_wgrad_kernel<T>, tile_grid(rows, C / Traits<T>::VW, t9, 9), st, x, dz, part, N, H, W, C, xps, OH,
-        OW, zps, t9);
-  }
-  const int tcl = tile_log2(C / kWgC);
-  const dim3 grid = tile_grid(rows, C / kWgC, tcl, KH == 7 ? 7 : 1);
-  if (KH == 7) {
-    return launch(dw_wgrad_row_kernel<T, 7, 1>, grid, st, x, dz, part, RL, bias, N, H, W, C, xps, OH, OW, zps, tcl);
-  }
-  if (bias) return -1;
-  DW_DISPATCH35((dw_wgrad_kernel<T, K_, S_><<<grid, 256, 0, st>>>(x, dz, part, N, H, W, C, xps, OH, OW, zps, tcl)))
-  return (int)hipGetLastError();
+  return by_k_s(KH, S, [&](auto k, auto s) {
+    constexpr int K = decltype(k)::value, S_ = decltype(s)::value;
+    constexpr int CU = K == 9 ? Traits<T>::VW : kWgC;  // channels per thread
+    const int tcl = tile_log2(C / CU);
+    const dim3 grid = tile_grid(rows, C / CU, tcl, K >= 7 ? K : 1);  // K >= 7: one filter row per blockIdx.z
+    if constexpr (K == 9) {
+      return launch(dw9_wgrad_kernel<T>, grid, st, x, dz, part, N, H, W, C, xps, OH, OW, zps, tcl);
+    } else if constexpr (K == 7) {
+      return launch(dw_wgrad_row_kernel<T, 7, 1>, grid, st, x, dz, part, RL, bias, N, H, W, C, xps, OH, OW, zps, tcl);
+    } else {
+      return launch(dw_wgrad_kernel<T, K, S_>, grid, st, x, dz, part, N, H, W, C, xps, OH, OW, zps, tcl);
+    }
+  });
 }
 
 // the one-launch inference forwards: EPI_ACT, or EPI_ACTBN (9 x 9 only)
@@ -759,17 +763,15 @@ DMY_API int dmy_dwconv_wgrad_finalize(const float* part, int rows, int C, int KH
                                       void* stream) {
   if (rows < 1 || C < 1 || KH < 1 || KW < 1) return -1;
   const int KK = KH * KW;
-  dw_wgrad_finalize_kernel<<<ceil_div((long)KK * C, 256), 256, 0, (hipStream_t)stream>>>(part, rows, C, KK, (long)KK * C,
-                                                                                        dw, accumulate, nullptr, 0);
-  return (int)hipGetLastError();
+  return launch(dw_wgrad_finalize_kernel, ceil_div((long)KK * C, 256), stream, part, rows, C, KK, (long)KK * C, dw,
+                accumulate, nullptr, 0);
 }
 
 DMY_API int dmy_dwconv_wgrad_bias_finalize(const float* part, int rows, int C, int KH, int KW, float* dw, int accumulate,
                                            float* dbias, int bias_accumulate, void* stream) {
   if (rows < 1 || C < 1 || KH < 1 || KW < 1 || !dbias) return -1;
   const int KK = KH * KW;
-  dw_wgrad_finalize_kernel<<<ceil_div((long)(KK + 1) * C, 256), 256, 0, (hipStream_t)stream>>>(
-      part, rows, C, KK, (long)(KK + 1) * C, dw, accumulate, dbias, bias_accumulate);
-  return (int)hipGetLastError();
+  return launch(dw_wgrad_finalize_kernel, ceil_div((long)(KK + 1) * C, 256), stream, part, rows, C, KK,
+                (long)(KK + 1) * C, dw, accumulate, dbias, bias_accumulate);
 }
 

@@ -969,20 +969,14 @@ def _conv_wgrad(ctx, dt, x, dz, dzps, with_bias=False):
         dw, zeroed = _wgrad_target(ctx, (K, 1, k, k), dev)
         _dw_check(dt, x, dz, dz, g, g.xps, dzps)
         P = call('dmy_dwconv_wgrad_rows', g.M, C)
-        if with_bias:  # rows of (k * k + 1) * C: the bias gradient's share follows the filter taps
-            part, dbias = f32(P * (k * k + 1) * C, dev), _pgrad(ctx, 0, K, dev)
-            KernelTimer.run('dwconv_wgrad', g.flops(), 'dmy_dwconv_wgrad_bias', dt, ptr(x), ptr(dz), ptr(part), *g.dw(),
-                            dzps, stream(), tag=g.tag(),
-                            nbytes=x.element_size() * (g.N * g.H * g.W * C + g.M * C) + 4 * (k * k + 1) * C)
-            call('dmy_dwconv_wgrad_bias_finalize', ptr(part), P, C, k, k, ptr(dw), int(zeroed), ptr(dbias), 0,
-                 stream())
-            return dw, dbias
-        part = f32(P * k * k * C, dev)
-        KernelTimer.run('dwconv_wgrad', g.flops(), 'dmy_dwconv_wgrad', dt, ptr(x), ptr(dz), ptr(part), *g.dw(), dzps,
-                        stream(), tag=g.tag(),
-                        nbytes=x.element_size() * (g.N * g.H * g.W * C + g.M * C) + 4 * k * k * C)
-        call('dmy_dwconv_wgrad_finalize', ptr(part), P, C, k, k, ptr(dw), int(zeroed), stream())
-        return dw, None
+        # with_bias: rows of (k * k + 1) * C, the bias gradient's share follows the filter taps
+        row, sfx = (k * k + int(with_bias)) * C, '_bias' if with_bias else ''
+        part, dbias = f32(P * row, dev), _pgrad(ctx, 0, K, dev) if with_bias else None
+        KernelTimer.run('dwconv_wgrad', g.flops(), 'dmy_dwconv_wgrad' + sfx, dt, ptr(x), ptr(dz), ptr(part), *g.dw(), dzps,
+                        stream(), tag=g.tag(), nbytes=x.element_size() * (g.N * g.H * g.W * C + g.M * C) + 4 * row)
+        call(f'dmy_dwconv_wgrad{sfx}_finalize', ptr(part), P, C, k, k, ptr(dw), int(zeroed),
+             *((ptr(dbias), 0) if with_bias else ()), stream())
+        return dw, dbias
     dw, zeroed = _wgrad_target(ctx, (K, C, k, k), dev)
     if g.s2d:
         dwo = f32(K * 9 * g.s2d, dev)

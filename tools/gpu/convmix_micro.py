@@ -7,7 +7,9 @@ algorithmic bytes (dmy_slice_copy: one read, one write, over as many rows as mov
 next to dmy_bn_act_fwd / dmy_bn_bwd_reduce / dmy_bn_bwd_apply on the same tensors (up to 2048 bf16 channels, the widest
 the bn.hip vector kernels take).  A report, not a gate.
 
-    python tools/gpu/convmix_micro.py [--batch 32] [--reps 7] [--what dw actbn]
+    python tools/gpu/convmix_micro.py [--batch 32] [--reps 7] [--what dw actbn] [--ks 3 5 --stride 2]
+
+--ks times the depthwise launches of those filter sizes (3 / 5 / 7 / 9) at --stride instead of the default 9x9 / 7x7 sets.
 """
 import argparse
 import os
@@ -43,11 +45,12 @@ def copier(src, dst, M, C, tensors):
     return lambda: call('dmy_slice_copy', 1, ptr(src), C, ptr(dst), C, rows, C, None, 0, 0, 0.0, 0, stream())
 
 
-def dw(N, H, W, C, reps, ks):
-    M, es = N * H * W, 2
-    x, dz, y = act(N, C, H, W), act(N, C, H, W), act(N, C, H, W)
+def dw(N, H, W, C, reps, ks, S=1):
+    OH, OW = (H - 1) // S + 1, (W - 1) // S + 1  # padding k // 2, k odd
+    M, es = N * OH * OW, 2
+    x, dz, y = act(N, C, H, W), act(N, C, OH, OW), act(N, C, H, W)
     b = torch.randn(C, device='cuda')
-    tag = f'{N} x {H}^2 x {C}'
+    tag = f'{N} x {H}^2 x {C}' + (f' s{S}' if S != 1 else '')
     copy = copier(x, y, M, C, 2)
     for K in ks:
         P = K // 2
@@ -55,7 +58,7 @@ def dw(N, H, W, C, reps, ks):
         rows, frows = call('dmy_dwconv_wgrad_rows', M, C), call('dmy_dwconv_fwd_rows', M, C)
         part = torch.empty(rows * K * K * C, device='cuda')
         ps, pq = torch.empty(frows * C, device='cuda'), torch.empty(frows * C, device='cuda')
-        geo = (N, H, W, C, C, K, K, 1, P, H, W, C)
+        geo = (N, H, W, C, C, K, K, S, P, OH, OW, C)
         ab(f'{tag} {K}x{K} forward + BN partial rows', lambda: call('dmy_dwconv_fwd', 1, ptr(x), ptr(w), ptr(b), ptr(y), ptr(ps),
                                                                    ptr(pq), *geo, stream()), copy, 2 * M * C * es, reps)
         if K == 9:
@@ -68,7 +71,7 @@ def dw(N, H, W, C, reps, ks):
         ab(f'{tag} {K}x{K} weight-grad (partial rows)', lambda: call('dmy_dwconv_wgrad', 1, ptr(x), ptr(dz), ptr(part), *geo,
                                                                     stream()), copy, 2 * M * C * es, reps)
         del part
-    if len(ks) == 2:
+    if sorted(ks) == [7, 9]:
         print(f'\n{tag}: time per tap, 9x9 (us / 81) against 7x7 (us / 49)')
         for what in ('forward + BN partial rows', 'data-grad', 'weight-grad (partial rows)'):
             t9, t7 = RESULTS[f'{tag} 9x9 {what}'] / 81, RESULTS[f'{tag} 7x7 {what}'] / 49
@@ -120,10 +123,12 @@ if __name__ == '__main__':
     ap.add_argument('--what', nargs='+', default=['dw', 'actbn'], choices=['dw', 'actbn'])
     ap.add_argument('--batch', type=int, default=32)
     ap.add_argument('--reps', type=int, default=7)
+    ap.add_argument('--ks', type=int, nargs='+', choices=[3, 5, 7, 9], help='time these depthwise filter sizes only')
+    ap.add_argument('--stride', type=int, default=1, choices=[1, 2], help='with --ks (7 and 9 are stride 1 only)')
     a = ap.parse_args()
     print('| launch | time | algorithmic bytes | rate | copy of the same bytes | ratio |\n|---|---|---|---|---|---|')
     for (H, C, ks) in ((48, 2048, (9,)), (192, 248, (9, 7))):
         if 'dw' in a.what:
-            dw(a.batch, H, H, C, a.reps, ks)
+            dw(a.batch, H, H, C, a.reps, a.ks or ks, a.stride if a.ks else 1)
         if 'actbn' in a.what:
             actbn(a.batch, H, H, C, a.reps)
