@@ -353,7 +353,7 @@ DMY_API int dmy_adapt_gate_fwd(int dtype, int L, const void* x0, long x0ps, int 
     if (!fill_levels<T>(A, L, xs, xps, Cs, nullptr, nullptr)) return -1;
     auto go = [&](auto nl) { return launch(adapt_gate_fwd_kernel<T, decltype(nl)::value>, grid, stream, A, wm, wmps, W,
         b, y, yps, a, M, sh); };
-    return L == 2 ? go(Width<2>{}) : go(Width<3>{});
+    return L == 2 ? go(Int<2>{}) : go(Int<3>{});
   });
 }
 
@@ -378,7 +378,7 @@ DMY_API int dmy_adapt_gate_bwd(int dtype, int L, const void* dy, long dps, const
     if (!fill_levels<T>(A, L, xs, xps, Cs, dxs, dxps)) return -1;
     auto go = [&](auto nl) { return launch(adapt_gate_bwd_kernel<T, decltype(nl)::value>, grid, stream, A, dy, dps, a,
         wm, wmps, W, accumulate, dwm, dwmps, pdw, pdb, M, sh); };
-    return L == 2 ? go(Width<2>{}) : go(Width<3>{});
+    return L == 2 ? go(Int<2>{}) : go(Int<3>{});
   });
 }
 
@@ -395,7 +395,7 @@ DMY_API int dmy_adapt_add_fwd(int dtype, int n, const void* x0, long x0ps, const
     if (!fill_levels<T>(A, n, xs, xps, Cs, nullptr, nullptr)) return -1;
     auto go = [&](auto ni) { return launch(adapt_add_fwd_kernel<T, decltype(ni)::value>, grid, stream, A, w, eps, y,
         yps, M, C); };
-    return n == 2 ? go(Width<2>{}) : go(Width<3>{});
+    return n == 2 ? go(Int<2>{}) : go(Int<3>{});
   });
 }
 
@@ -416,7 +416,7 @@ DMY_API int dmy_adapt_add_bwd(int dtype, int n, const void* dy, long dps, const 
     if (!fill_levels<T>(A, n, xs, xps, Cs, dxs, dxps)) return -1;
     auto go = [&](auto ni) { return launch(adapt_add_bwd_kernel<T, decltype(ni)::value>, grid, stream, A, dy, dps, w,
         eps, accumulate, part, M, C); };
-    return n == 2 ? go(Width<2>{}) : go(Width<3>{});
+    return n == 2 ? go(Int<2>{}) : go(Int<3>{});
   });
 }
 

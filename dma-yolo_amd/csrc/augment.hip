@@ -9,7 +9,7 @@
 // every product / difference rounded separately (no contraction), and mixup's float64 blend truncated to uint8 --
 // so the batch equals the host path bit for bit (tests/test_gpu_augment.py).  One thread per output pixel; the
 // canvases are read through L2 (4 taps x 3 bytes), the output planes are written coalesced.
-#include "common.h"
+#include "launch.h"
 
 // Every float / double operation here must round exactly as the host restatement's numpy ops do: this file is
 // built with -ffp-contract=off (__graft_entry__ FILE_FLAGS) -- with the library's -ffp-contract=fast, 1 - s * h
@@ -218,8 +218,7 @@ DMY_API long dmy_mosaic_desc_bytes() { return (long)sizeof(MosaicDesc); }
 DMY_API int dmy_mosaic_compose(const void* descs, int n, int S2, void* stream) {
   if (n <= 0 || S2 <= 0) return 0;
   const dim3 grid((unsigned)(((long)S2 * S2 + 255) / 256), (unsigned)n);
-  mosaic_compose_kernel<<<grid, 256, 0, (hipStream_t)stream>>>((const MosaicDesc*)descs);
-  return (int)hipGetLastError();
+  return launch(mosaic_compose_kernel, grid, stream, descs);
 }
 
 DMY_API long dmy_aug_desc_bytes() { return (long)sizeof(AugDesc); }
@@ -227,7 +226,6 @@ DMY_API long dmy_aug_desc_bytes() { return (long)sizeof(AugDesc); }
 // descs: device array of n AugDesc; out: uint8 [n, 3, OH, OW]
 DMY_API int dmy_augment_batch(const void* descs, int n, void* out, int OH, int OW, void* stream) {
   if (n <= 0 || OH <= 0 || OW <= 0) return 0;
-  hipStream_t st = (hipStream_t)stream;
   if (!tables_ready) {  // OpenCV RGB2HSV_b tables: saturate_cast<int>((255 << 12) / (1. * i)), (180 << 12) / (6. * i)
     int sdiv[256], hdiv[256];
     sdiv[0] = hdiv[0] = 0;
@@ -237,10 +235,9 @@ DMY_API int dmy_augment_batch(const void* descs, int n, void* out, int OH, int O
     }
     if (hipMemcpyToSymbol(HIP_SYMBOL(c_sdiv), sdiv, sizeof(sdiv)) != hipSuccess ||
         hipMemcpyToSymbol(HIP_SYMBOL(c_hdiv), hdiv, sizeof(hdiv)) != hipSuccess)
-      return (int)hipErrorInvalidValue;
+      return kInvalid;
     tables_ready = true;
   }
   const dim3 grid((unsigned)((OH * OW + 255) / 256), (unsigned)n);
-  augment_batch_kernel<<<grid, 256, 0, st>>>((const AugDesc*)descs, (unsigned char*)out, OH, OW);
-  return (int)hipGetLastError();
+  return launch(augment_batch_kernel, grid, stream, descs, out, OH, OW);
 }

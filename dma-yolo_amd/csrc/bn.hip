@@ -523,47 +523,37 @@ DMY_API int dmy_bn_stats(int dtype, const void* z, long zps, long M, int C, floa
   return by_dtype(dtype, kInvalid, [&](auto tag) {
     using T = typename decltype(tag)::type;
     constexpr int VW = Traits<T>::VW;
-    hipStream_t st = (hipStream_t)stream;
-    if (vec_ok(VW, C, {zps}, {}, {z}) && C / VW <= 256) {
-      bn_bwd_reduce_vec<T, true><<<row_grid(M, C, VW, kRedCap), 256, 0, st>>>(
-          (const T*)z, zps, (const T*)z, zps, nullptr, nullptr, nullptr, nullptr, 0, M, C, psum, psq, 0);
-    } else {
-      const int P = dmy_bn_partial_rows(M);
-      const int rpb = (int)((M + P - 1) / P);
-      bn_stats_kernel<T><<<dim3(P, ceil_div(C, 64)), 256, 0, st>>>((const T*)z, zps, M, C, rpb, psum, psq);
-    }
-    return (int)hipGetLastError();
+    if (vec_ok(VW, C, {zps}, {}, {z}) && C / VW <= 256)
+      return launch(bn_bwd_reduce_vec<T, true>, row_grid(M, C, VW, kRedCap), stream, z, zps, z, zps, nullptr, nullptr,
+                    nullptr, nullptr, 0, M, C, psum, psq, 0);
+    const int P = dmy_bn_partial_rows(M);
+    const int rpb = (int)((M + P - 1) / P);
+    return launch(bn_stats_kernel<T>, dim3(P, ceil_div(C, 64)), stream, z, zps, M, C, rpb, psum, psq);
   });
 }
 
 DMY_API int dmy_bn_finalize(const float* psum, const float* psq, int P, int C, double count, const float* gamma,
                             const float* beta, float* rmean, float* rvar, long long* nbt, float momentum, float eps,
                             int update, float* mean, float* invstd, float* scale, float* shift, void* stream) {
-  bn_finalize_kernel<<<C, 256, 0, (hipStream_t)stream>>>(psum, psq, P, C, count, gamma, beta, rmean, rvar, nbt,
-                                                         momentum, eps, update, mean, invstd, scale, shift);
-  return (int)hipGetLastError();
+  return launch(bn_finalize_kernel, C, stream, psum, psq, P, C, count, gamma, beta, rmean, rvar, nbt, momentum, eps, update,
+                mean, invstd, scale, shift);
 }
 
 DMY_API int dmy_bn_eval_coef(const float* gamma, const float* beta, const float* rmean, const float* rvar, float eps,
                              int C, float* scale, float* shift, void* stream) {
-  bn_eval_coef_kernel<<<ceil_div(C, 256), 256, 0, (hipStream_t)stream>>>(gamma, beta, rmean, rvar, eps, C, scale, shift);
-  return (int)hipGetLastError();
+  return launch(bn_eval_coef_kernel, ceil_div(C, 256), stream, gamma, beta, rmean, rvar, eps, C, scale, shift);
 }
-
 
 DMY_API int dmy_bn_act_fwd(int dtype, const void* z, long zps, const float* scale, const float* shift, int act,
                            const void* res, long rps, void* y, long yps, long M, int C, void* stream) {
   return by_dtype(dtype, kInvalid, [&](auto tag) {
     using T = typename decltype(tag)::type;
     constexpr int VW = Traits<T>::VW;
-    hipStream_t st = (hipStream_t)stream;
     if (vec_ok(VW, C, {zps, yps, res ? rps : 0}, {}, {z, y, res}) && C / VW <= 256)
-      bn_act_fwd_vec<T><<<row_grid(M, C, VW, kEwCap), 256, 0, st>>>((const T*)z, zps, scale, shift, act, (const T*)res, rps,
-                                                                    (T*)y, yps, M, C, kRevAct);
-    else
-      bn_act_fwd_scalar<T><<<grid_cap(ceil_div(M * C, 256), 8192), 256, 0, st>>>((const T*)z, zps, scale, shift, act,
-                                                                                 (const T*)res, rps, (T*)y, yps, M, C);
-    return (int)hipGetLastError();
+      return launch(bn_act_fwd_vec<T>, row_grid(M, C, VW, kEwCap), stream, z, zps, scale, shift, act, res, rps, y, yps, M,
+                    C, kRevAct);
+    return launch(bn_act_fwd_scalar<T>, grid_cap(ceil_div(M * C, 256), 8192), stream, z, zps, scale, shift, act, res, rps,
+                  y, yps, M, C);
   });
 }
 
@@ -575,14 +565,13 @@ DMY_API int dmy_bn_act_fwd_f8(const void* z, long zps, const float* scale, const
   if (C / 8 > 256 || !vec_ok(8, C, {zps, yps, res ? rps : 0}, {}, {z, y, res}) || ((uintptr_t)y8 & 7) || !(headroom >= 1.f))
     return kInvalid;
   const int G = dmy_bn_act_f8_blocks();
-  bn_act_fwd_f8_kernel<<<G, 256, 0, (hipStream_t)stream>>>((const bf16*)z, zps, scale, shift, act, (const bf16*)res, rps,
-                                                          (bf16*)y, yps, M, C, (unsigned char*)y8, pmax, G, nmax, used,
-                                                          headroom, nsat);
-  return (int)hipGetLastError();
+  return launch(bn_act_fwd_f8_kernel, G, stream, z, zps, scale, shift, act, res, rps, y, yps, M, C, y8, pmax, G, nmax, used,
+                headroom, nsat);
 }
 
-// Partial rows written by dmy_bn_bwd_reduce / dmy_bn_stats for these exact arguments.
+// Partial rows written by dmy_bn_bwd_reduce / dmy_bn_stats for these exact arguments; 0 for a dtype they refuse.
 DMY_API int dmy_bn_reduce_rows(int dtype, const void* z, long zps, const void* dy, long dps, long M, int C) {
+  if (dtype != 0 && dtype != 1) return 0;
   const int VW = vec_width(dtype);
   if (vec_ok(VW, C, {zps, dy ? dps : 0}, {}, {z, dy}) && C / VW <= 256) return row_grid(M, C, VW, kRedCap);
   return dmy_bn_partial_rows(M);
@@ -594,17 +583,13 @@ DMY_API int dmy_bn_bwd_reduce(int dtype, const void* z, long zps, const void* dy
   return by_dtype(dtype, kInvalid, [&](auto tag) {
     using T = typename decltype(tag)::type;
     constexpr int VW = Traits<T>::VW;
-    hipStream_t st = (hipStream_t)stream;
-    if (vec_ok(VW, C, {zps, dps}, {}, {z, dy}) && C / VW <= 256) {
-      bn_bwd_reduce_vec<T, false><<<row_grid(M, C, VW, kRedCap), 256, 0, st>>>(
-          (const T*)z, zps, (const T*)dy, dps, scale, shift, mean, invstd, act, M, C, pdb, pdg, kRevReduce);
-    } else {
-      const int P = dmy_bn_partial_rows(M);
-      const int rpb = (int)((M + P - 1) / P);
-      bn_bwd_reduce_kernel<T><<<dim3(P, ceil_div(C, 64)), 256, 0, st>>>((const T*)z, zps, (const T*)dy, dps, scale, shift,
-                                                                        mean, invstd, act, M, C, rpb, pdb, pdg);
-    }
-    return (int)hipGetLastError();
+    if (vec_ok(VW, C, {zps, dps}, {}, {z, dy}) && C / VW <= 256)
+      return launch(bn_bwd_reduce_vec<T, false>, row_grid(M, C, VW, kRedCap), stream, z, zps, dy, dps, scale, shift, mean,
+                    invstd, act, M, C, pdb, pdg, kRevReduce);
+    const int P = dmy_bn_partial_rows(M);
+    const int rpb = (int)((M + P - 1) / P);
+    return launch(bn_bwd_reduce_kernel<T>, dim3(P, ceil_div(C, 64)), stream, z, zps, dy, dps, scale, shift, mean, invstd,
+                  act, M, C, rpb, pdb, pdg);
   });
 }
 
@@ -613,17 +598,13 @@ DMY_API int dmy_colsum2_rows(long P) { return (int)(P < 256 ? P : 256); }
 DMY_API int dmy_colsum2(const float* a, const float* b, long P, int C, float* oa, float* ob, void* stream) {
   const int S = dmy_colsum2_rows(P);
   const int rows = (int)((P + S - 1) / S);
-  dim3 grid(S, ceil_div(C, 64));
-  colsum2_kernel<<<grid, 256, 0, (hipStream_t)stream>>>(a, b, P, C, rows, oa, ob);
-  return (int)hipGetLastError();
+  return launch(colsum2_kernel, dim3(S, ceil_div(C, 64)), stream, a, b, P, C, rows, oa, ob);
 }
 
 DMY_API int dmy_bn_bwd_finalize(const float* pdb, const float* pdg, int P, int C, double count, const float* gamma,
                                 const float* invstd, float* dgamma, float* dbeta, float* ca, float* cb, float* cc,
                                 void* stream) {
-  bn_bwd_finalize_kernel<<<C, 256, 0, (hipStream_t)stream>>>(pdb, pdg, P, C, count, gamma, invstd, dgamma, dbeta, ca,
-                                                             cb, cc);
-  return (int)hipGetLastError();
+  return launch(bn_bwd_finalize_kernel, C, stream, pdb, pdg, P, C, count, gamma, invstd, dgamma, dbeta, ca, cb, cc);
 }
 
 DMY_API int dmy_bn_bwd_apply(int dtype, const void* z, long zps, const void* dy, long dps, const float* scale,
@@ -632,14 +613,11 @@ DMY_API int dmy_bn_bwd_apply(int dtype, const void* z, long zps, const void* dy,
   return by_dtype(dtype, kInvalid, [&](auto tag) {
     using T = typename decltype(tag)::type;
     constexpr int VW = Traits<T>::VW;
-    hipStream_t st = (hipStream_t)stream;
     if (vec_ok(VW, C, {zps, dps, dzps}, {}, {z, dy, dz}) && C / VW <= 256)
-      bn_bwd_apply_vec<T><<<row_grid(M, C, VW, kEwCap), 256, 0, st>>>((const T*)z, zps, (const T*)dy, dps, scale, shift, mean,
-                                                                      invstd, act, ca, cb, cc, (T*)dz, dzps, M, C, kRevApply);
-    else
-      bn_bwd_apply_scalar<T><<<grid_cap(ceil_div(M * C, 256), 8192), 256, 0, st>>>(
-          (const T*)z, zps, (const T*)dy, dps, scale, shift, mean, invstd, act, ca, cb, cc, (T*)dz, dzps, M, C);
-    return (int)hipGetLastError();
+      return launch(bn_bwd_apply_vec<T>, row_grid(M, C, VW, kEwCap), stream, z, zps, dy, dps, scale, shift, mean, invstd,
+                    act, ca, cb, cc, dz, dzps, M, C, kRevApply);
+    return launch(bn_bwd_apply_scalar<T>, grid_cap(ceil_div(M * C, 256), 8192), stream, z, zps, dy, dps, scale, shift, mean,
+                  invstd, act, ca, cb, cc, dz, dzps, M, C);
   });
 }
 
@@ -661,8 +639,7 @@ __global__ void reduce_rows_kernel(const float* __restrict__ part, int P, int C,
 }
 
 DMY_API int dmy_reduce_rows(const float* part, int P, int C, float* out, int accumulate, void* stream) {
-  reduce_rows_kernel<<<C, 256, 0, (hipStream_t)stream>>>(part, P, C, out, accumulate);
-  return (int)hipGetLastError();
+  return launch(reduce_rows_kernel, C, stream, part, P, C, out, accumulate);
 }
 
 // ---------------------------------------------------------------- SCConv gate with k3's BatchNorm folded in
@@ -813,10 +790,8 @@ DMY_API int dmy_scgate_bn_rows(int N, int H, int W, int C) { return row_grid((lo
 DMY_API int dmy_scgate_bn_fwd(const void* x, long xps, const void* z, const float* scale, const float* shift,
                               const void* g, void* out, int N, int H, int W, int C, int GH, int GW, void* stream) {
   if (!scgate_bn_ok(C, xps, x, z, g, out)) return kInvalid;
-  const int grid = dmy_scgate_bn_rows(N, H, W, C);
-  scgate_bn_fwd_kernel<<<grid, 256, 0, (hipStream_t)stream>>>((const bf16*)x, xps, (const bf16*)z, scale, shift,
-                                                              (const bf16*)g, (bf16*)out, N, H, W, C, GH, GW);
-  return (int)hipGetLastError();
+  return launch(scgate_bn_fwd_kernel, dmy_scgate_bn_rows(N, H, W, C), stream, x, xps, z, scale, shift, g, out, N, H, W, C,
+                GH, GW);
 }
 
 DMY_API int dmy_scgate_bn_bwd(const void* x, long xps, const void* z, const float* scale, const float* shift,
@@ -824,9 +799,6 @@ DMY_API int dmy_scgate_bn_bwd(const void* x, long xps, const void* z, const floa
                               void* dpre, int N, int H, int W, int C, int GH, int GW, float* pdb, float* pdg,
                               void* stream) {
   if (!scgate_bn_ok(C, xps, x, z, g, du3) || !vec_ok(8, C, {}, {}, {dout, dpre})) return kInvalid;
-  const int grid = dmy_scgate_bn_rows(N, H, W, C);
-  scgate_bn_bwd_kernel<<<grid, 256, 0, (hipStream_t)stream>>>((const bf16*)x, xps, (const bf16*)z, scale, shift, mean,
-                                                              invstd, (const bf16*)g, (const bf16*)dout, (bf16*)du3,
-                                                              (bf16*)dpre, N, H, W, C, GH, GW, pdb, pdg);
-  return (int)hipGetLastError();
+  return launch(scgate_bn_bwd_kernel, dmy_scgate_bn_rows(N, H, W, C), stream, x, xps, z, scale, shift, mean, invstd, g, dout,
+                du3, dpre, N, H, W, C, GH, GW, pdb, pdg);
 }

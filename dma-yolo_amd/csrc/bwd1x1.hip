@@ -355,9 +355,9 @@ inline int grid_blocks(long M, int K, int C) {
 }
 
 template <int K, int C>
-int launch(const bf16* dy, long dps, const bf16* z, const bf16* x, long xps, const bf16* wt, const float* scale,
-           const float* shift, const float* mean, const float* invstd, int act, const float* ca, const float* cb,
-           const float* cc, bf16* dx, long bps, int acc, float* dw, float* ws, long M, hipStream_t st) {
+int run(const void* dy, long dps, const void* z, const void* x, long xps, const void* wt, const float* scale,
+        const float* shift, const float* mean, const float* invstd, int act, const float* ca, const float* cb,
+        const float* cc, void* dx, long bps, int acc, float* dw, float* ws, long M, void* stream) {
   constexpr Plan pl = plan(K, C);
   constexpr int CB = pl.cb, TP = pl.tp, PX = pl.px, NS = C / CB;
   using S = Shape<K, CB, TP, PX>;
@@ -368,12 +368,11 @@ int launch(const bf16* dy, long dps, const bf16* z, const bf16* x, long xps, con
     raised = true;
   }
   const int nb = grid_blocks(M, K, C);
-  conv1x1_bwd_bn<K, CB, TP, PX><<<nb, 256, S::LDS, st>>>(
-      dy, dps, z, x, xps, wt, scale, shift, mean, invstd, act, ca, cb, cc, dx, bps, acc, dw, ws, M, ceil_div(M, TP), C,
-      NS, (unsigned)(2.0 * (double)M * dps), (unsigned)(2.0 * (double)M * K), (unsigned)(2.0 * (double)M * xps));
-  if (ws != nullptr)
-    wgrad_slots_reduce<<<ceil_div((long)K * C, 256), 256, 0, st>>>(ws, dw, K, C, CB, nb, NS);
-  return (int)hipGetLastError();
+  if (int e = launch(conv1x1_bwd_bn<K, CB, TP, PX>, nb, 256, S::LDS, stream, dy, dps, z, x, xps, wt, scale, shift, mean,
+                     invstd, act, ca, cb, cc, dx, bps, acc, dw, ws, M, ceil_div(M, TP), C, NS,
+                     (unsigned)(2.0 * (double)M * dps), (unsigned)(2.0 * (double)M * K), (unsigned)(2.0 * (double)M * xps)))
+    return e;
+  return ws != nullptr ? launch(wgrad_slots_reduce, ceil_div((long)K * C, 256), stream, ws, dw, K, C, CB, nb, NS) : 0;
 }
 }  // namespace b1
 }  // namespace
@@ -399,20 +398,14 @@ DMY_API int dmy_conv1x1_bwd_bn(const void* dy, long dps, const void* z, const vo
                                float* dw, float* ws, long ws_elems, long M, int K, int C, void* stream) {
   if (!dmy_conv1x1_bwd_bn_ok(M, K, C, dps, xps, bps, dy, z, x, dx)) return -1;
   if (ws != nullptr && ws_elems < dmy_conv1x1_bwd_bn_ws_elems(M, K, C)) return -1;
-  hipStream_t st = (hipStream_t)stream;
-#define B1_GO(K_, C_)                                                                                                 \
-  if (K == K_ && C == C_)                                                                                            \
-    return b1::launch<K_, C_>((const bf16*)dy, dps, (const bf16*)z, (const bf16*)x, xps, (const bf16*)wt, scale,     \
-                              shift, mean, invstd, act, ca, cb, cc, (bf16*)dx, bps, accumulate, dw, ws, M, st);
-  B1_GO(64, 64)
-  B1_GO(128, 64)
-  B1_GO(64, 128)
-  B1_GO(128, 128)
-  B1_GO(128, 256)
-  B1_GO(128, 512)
-  B1_GO(256, 128)
-  B1_GO(256, 256)
-  B1_GO(64, 256)
-#undef B1_GO
-  return -1;
+  // the (K, C) pairs that b1::plan builds, and no other
+  return by_int<64, 128, 256>(K, -1, [&](auto k) {
+    return by_int<64, 128, 256, 512>(C, -1, [&](auto c) {
+      constexpr int K_ = decltype(k)::value, C_ = decltype(c)::value;
+      if constexpr (b1::plan(K_, C_).cb == 0) return -1;
+      else
+        return b1::run<K_, C_>(dy, dps, z, x, xps, wt, scale, shift, mean, invstd, act, ca, cb, cc, dx, bps, accumulate,
+                               dw, ws, M, stream);
+    });
+  });
 }

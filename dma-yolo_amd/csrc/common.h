@@ -179,8 +179,6 @@ DEV unsigned pack4_e4m3(float a, float b, float c, float d) {  // OCP e4m3fn, ro
 }
 DEV float nanmax(float a, float b) { return (a != a || b != b) ? __builtin_nanf("") : fmaxf(a, b); }
 
-#define HIP_LAUNCH_CHECK() return (int)hipGetLastError()
-
 static inline int ceil_div(long a, long b) { return (int)((a + b - 1) / b); }
 static inline int grid_cap(long blocks, int cap = 4096) { return (int)(blocks < cap ? (blocks < 1 ? 1 : blocks) : cap); }
 

@@ -30,7 +30,6 @@ inline int num_cus() {
   return n;
 }
 
-template <int N> using Int = std::integral_constant<int, N>;  // a tile size as a lambda argument
 inline bool is_p1(const Geom& g) { return g.KH == 1 && g.KW == 1 && g.S == 1 && g.P == 0; }
 // byte extents of the bf16 operands of g (H x W x C gather tensor, OH x OW x K output, K x KH x KW x C weights): the
 // num_records of their buffer descriptors, which must stay below the out-of-range offset v3::kBufOob

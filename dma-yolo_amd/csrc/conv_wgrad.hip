@@ -1276,8 +1276,7 @@ int conv_wgrad_route(int dtype, const void* x, const void* dy, int N, int H, int
 DMY_API int dmy_conv_wprep_fp8(const float* w_oihw, void* w8, float* wscale, int K, int C, int KH, int KW,
                                void* stream) {
   if (C % 4 != 0) return (int)hipErrorInvalidValue;
-  wprep_fp8_kernel<<<K, 256, 0, (hipStream_t)stream>>>(w_oihw, (unsigned char*)w8, wscale, C, KH, KW);
-  return (int)hipGetLastError();
+  return launch(wprep_fp8_kernel, K, stream, w_oihw, w8, wscale, C, KH, KW);
 }
 
 // the weight-grad entries' body: g carries the flags; det = deterministic mode, whose splits (when more than one)
@@ -1352,15 +1351,12 @@ DMY_API int dmy_conv_wprep_s2d(int dtype, const float* w_oihw, void* w_s2d, int 
 }
 
 DMY_API int dmy_conv_wgrad_s2d_to_oihw(const float* dw_s2d, float* dw_oihw, int K, int C, int Cs, void* stream) {
-  wgrad_s2d_to_oihw_kernel<<<grid_cap(ceil_div((long)K * C * 36, 256), 1024), 256, 0, (hipStream_t)stream>>>(
-      dw_s2d, dw_oihw, K, C, Cs);
-  return (int)hipGetLastError();
+  return launch(wgrad_s2d_to_oihw_kernel, grid_cap(ceil_div((long)K * C * 36, 256), 1024), stream, dw_s2d, dw_oihw, K, C,
+                Cs);
 }
 
 DMY_API int dmy_conv_wgrad_to_oihw(const float* dw_ohwi, float* dw_oihw, int K, int C, int Cp, int KH, int KW,
                                    void* stream) {
   const long total = (long)K * C * KH * KW;
-  wgrad_to_oihw_kernel<<<grid_cap(ceil_div(total, 256), 1024), 256, 0, (hipStream_t)stream>>>(dw_ohwi, dw_oihw, K, C,
-                                                                                               Cp, KH, KW);
-  return (int)hipGetLastError();
+  return launch(wgrad_to_oihw_kernel, grid_cap(ceil_div(total, 256), 1024), stream, dw_ohwi, dw_oihw, K, C, Cp, KH, KW);
 }

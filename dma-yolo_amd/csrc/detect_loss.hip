@@ -664,8 +664,7 @@ DMY_API int dmy_build_targets(const float* targets, int nt, const float* anchors
                               int* b, int* a, int* gj, int* gi, int* tcls, float* tbox, float* anch, int* count,
                               void* stream) {
   TgtOut o{b, a, gj, gi, tcls, tbox, anch, count};
-  build_targets_kernel<<<1, 1024, 0, (hipStream_t)stream>>>(targets, nt, anchors, na, H, W, anchor_t, o);
-  return (int)hipGetLastError();
+  return launch(build_targets_kernel, 1, 1024, 0, stream, targets, nt, anchors, na, H, W, anchor_t, o);
 }
 
 DMY_API int dmy_yolo_loss_part_rows() { return 3 * LOSS_PMAX; }
@@ -704,17 +703,15 @@ DMY_API int dmy_yolo_loss_level_focal(int dtype, const void* p, long sb, long sa
 
 DMY_API int dmy_yolo_loss_finalize(const float* part, int nl, float box, float obj, float cls, float bs, float* loss,
                                    float* items, void* stream) {
-  loss_finalize_kernel<<<1, 256, 0, (hipStream_t)stream>>>(part, nl, box, obj, cls, bs, loss, items);
-  return (int)hipGetLastError();
+  return launch(loss_finalize_kernel, 1, stream, part, nl, box, obj, cls, bs, loss, items);
 }
 
 DMY_API int dmy_yolo_loss_finalize_balance(const float* part, int nl, float box, float obj, float cls, float bs,
                                            double* balance, int autobalance, int ssi, float* loss, float* items,
                                            void* stream) {
-  if (nl < 1 || nl > kBalLevels || balance == nullptr || ssi < 0 || ssi >= nl) return (int)hipErrorInvalidValue;
-  loss_finalize_balance_kernel<<<1, 256, 0, (hipStream_t)stream>>>(part, nl, box, obj, cls, bs, balance, autobalance,
-                                                                   ssi, loss, items);
-  return (int)hipGetLastError();
+  if (nl < 1 || nl > kBalLevels || balance == nullptr || ssi < 0 || ssi >= nl) return kInvalid;
+  return launch(loss_finalize_balance_kernel, 1, stream, part, nl, box, obj, cls, bs, balance, autobalance, ssi, loss,
+                items);
 }
 
 DMY_API int dmy_loss_grad(int dtype, const float* G, const float* up, void* dp, long n, void* stream) {
@@ -737,6 +734,5 @@ __global__ void siou_eval_kernel(const float* __restrict__ b1, const float* __re
 
 DMY_API int dmy_siou_eval(const float* b1, const float* b2, float* iou, float* grad, int n, void* stream) {
   if (n <= 0) return 0;
-  siou_eval_kernel<<<ceil_div(n, 256), 256, 0, (hipStream_t)stream>>>(b1, b2, iou, grad, n);
-  return (int)hipGetLastError();
+  return launch(siou_eval_kernel, ceil_div(n, 256), stream, b1, b2, iou, grad, n);
 }

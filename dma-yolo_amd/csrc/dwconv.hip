@@ -594,16 +594,13 @@ bool geom_ok(int dtype, int N, int H, int W, int C, long xps, int KH, int KW, in
   return true;
 }
 
-// f(Width<K>{}, Width<S>{}) for the (K, S) pairs geom_ok admits (K = 7 / 9 are stride 1 only), -1 for any other.  f is a
+// f(Int<K>{}, Int<S>{}) for the (K, S) pairs geom_ok admits (K = 7 / 9 are stride 1 only), -1 for any other.  f is a
 // generic lambda that holds the launch and returns the entry's int.
 template <typename F> int by_k_s(int K, int S, F&& f) {
-  if (K == 3 && S == 1) return f(Width<3>{}, Width<1>{});
-  if (K == 3 && S == 2) return f(Width<3>{}, Width<2>{});
-  if (K == 5 && S == 1) return f(Width<5>{}, Width<1>{});
-  if (K == 5 && S == 2) return f(Width<5>{}, Width<2>{});
-  if (K == 7 && S == 1) return f(Width<7>{}, Width<1>{});
-  if (K == 9 && S == 1) return f(Width<9>{}, Width<1>{});
-  return -1;
+  return by_int<3, 5, 7, 9>(K, -1, [&](auto k) {
+    if constexpr (decltype(k)::value >= 7) return by_int<1>(S, -1, [&](auto s) { return f(k, s); });
+    else return by_int<1, 2>(S, -1, [&](auto s) { return f(k, s); });
+  });
 }
 
 // the correlation kernel of (K, S): the 9 x 9 has a body of its own

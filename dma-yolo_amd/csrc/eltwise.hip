@@ -1252,7 +1252,6 @@ __global__ void __launch_bounds__(256) maxpool_chain3_lds(const T* __restrict__ 
 // Below, `v` is the vector contract with every base nullable: where it fails, by_dtype_vec picks the scalar twin (NV = 1).
 DMY_API int dmy_maxpool_fwd(int dtype, const void* x, long xps, void* y, long yps, unsigned char* arg, int N, int H,
                             int W, int C, int k, void* stream) {
-  hipStream_t st = (hipStream_t)stream;
   const int VW = vec_width(dtype);
   const bool v = vec_ok(VW, C, {xps, yps}, {}, {x, y});
   if (k < 1 || k > 15 || (k & 1) == 0) return kInvalid;  // uint8 window offsets
@@ -1260,42 +1259,25 @@ DMY_API int dmy_maxpool_fwd(int dtype, const void* x, long xps, void* y, long yp
     const unsigned gl = (unsigned)ceil_div(W, MP_TW) * ceil_div(H, MP_TH) * N * (C / VW);  // mp_tile order
     return by_dtype(dtype, kInvalid, [&](auto tag) {
       using T = typename decltype(tag)::type;
-#define MP_LDS(KS) maxpool_fwd_lds<T, KS><<<gl, 256, 0, st>>>((const T*)x, xps, (T*)y, yps, arg, H, W, C)
-      switch (k) {
-        case 3: MP_LDS(3); break;
-        case 5: MP_LDS(5); break;
-        case 7: MP_LDS(7); break;
-        case 9: MP_LDS(9); break;
-        case 11: MP_LDS(11); break;
-        default: MP_LDS(13); break;
-      }
-#undef MP_LDS
-      return (int)hipGetLastError();
+      return by_int<3, 5, 7, 9, 11, 13>(k, kInvalid, [&](auto ks) {
+        return launch(maxpool_fwd_lds<T, decltype(ks)::value>, gl, stream, x, xps, y, yps, arg, H, W, C);
+      });
     });
   }
   const int g = vgrid((long)N * H * W * C / (v ? VW : 1));
   return by_dtype_vec(dtype, v, kInvalid, [&](auto tag, auto nv) {
     using T = typename decltype(tag)::type;
     constexpr int NV = decltype(nv)::value;
-#define MP_FWD(KS) maxpool_fwd_kernel<T, NV, KS><<<g, 256, 0, st>>>((const T*)x, xps, (T*)y, yps, arg, N, H, W, C, k)
-    switch ((long)H * W * xps < (1L << 31) ? k : 0) {  // compile-time windows use 32-bit in-image offsets
-      case 3: MP_FWD(3); break;
-      case 5: MP_FWD(5); break;
-      case 7: MP_FWD(7); break;
-      case 9: MP_FWD(9); break;
-      case 11: MP_FWD(11); break;
-      case 13: MP_FWD(13); break;
-      default: MP_FWD(0); break;
-    }
-#undef MP_FWD
-    return (int)hipGetLastError();
+    // compile-time windows use 32-bit in-image offsets; 0 is the runtime window
+    return by_int<3, 5, 7, 9, 11, 13>((long)H * W * xps < (1L << 31) ? k : 0, Int<0>{}, [&](auto ks) {
+      return launch(maxpool_fwd_kernel<T, NV, decltype(ks)::value>, g, stream, x, xps, y, yps, arg, N, H, W, C, k);
+    });
   });
 }
 // y1 = pool(x), y2 = pool(y1), y3 = pool(y2) (k x k, stride 1, pad k / 2) in one launch, no argmax (inference); the
 // three outputs share the pixel stride yps (three channel slices of one concat buffer, or three tensors)
 DMY_API int dmy_maxpool_chain3_fwd(int dtype, const void* x, long xps, void* y1, void* y2, void* y3, long yps, int N,
                                    int H, int W, int C, int k, void* stream) {
-  hipStream_t st = (hipStream_t)stream;
   const int VW = vec_width(dtype);
   if (!vec_ok(VW, C, {xps, yps}, {}, {x, y1, y2, y3}) || (k != 3 && k != 5) || N * (C / VW) >= 65536) return kInvalid;
   // 16 x 32 tiles, or 8 x 16 when those leave most CUs idle (the 20^2 / 40^2 maps of batch-1 detect)
@@ -1304,21 +1286,16 @@ DMY_API int dmy_maxpool_chain3_fwd(int dtype, const void* x, long xps, void* y1,
   const unsigned gl = (unsigned)(cv * (small ? ceil_div(W, 16) * ceil_div(H, 8) : ceil_div(W, 32) * ceil_div(H, 16)));
   return by_dtype(dtype, kInvalid, [&](auto tag) {
     using T = typename decltype(tag)::type;
-#define MP3(KS, TH, TW) maxpool_chain3_lds<T, KS, TH, TW><<<gl, 256, 0, st>>>((const T*)x, xps, (T*)y1, (T*)y2, (T*)y3, yps, H, W, C)
-    if (k == 5) {
-      if (small) MP3(5, 8, 16);
-      else MP3(5, 16, 32);
-    } else {
-      if (small) MP3(3, 8, 16);
-      else MP3(3, 16, 32);
-    }
-#undef MP3
-    return (int)hipGetLastError();
+    return by_int<3, 5>(k, kInvalid, [&](auto ks) {
+      return by_flags(small, [&](auto sm) {
+        constexpr int TH = decltype(sm)::value ? 8 : 16;
+        return launch(maxpool_chain3_lds<T, decltype(ks)::value, TH, 2 * TH>, gl, stream, x, xps, y1, y2, y3, yps, H, W, C);
+      });
+    });
   });
 }
 DMY_API int dmy_maxpool_bwd(int dtype, const void* dy, long dps, const unsigned char* arg, void* dx, long dxps,
                             int accumulate, int N, int H, int W, int C, int k, void* stream) {
-  hipStream_t st = (hipStream_t)stream;
   const int VW = vec_width(dtype);
   const bool v = vec_ok(VW, C, {dps, dxps}, {}, {dy, dx});
   if (k < 1 || k > 15 || (k & 1) == 0) return kInvalid;
@@ -1326,23 +1303,15 @@ DMY_API int dmy_maxpool_bwd(int dtype, const void* dy, long dps, const unsigned 
     const unsigned gl = (unsigned)ceil_div(W, MP_TW) * ceil_div(H, MP_TH) * N * (C / VW);  // mp_tile order
     return by_dtype(dtype, kInvalid, [&](auto tag) {
       using T = typename decltype(tag)::type;
-#define MP_LDS(KS) maxpool_bwd_lds<T, KS><<<gl, 256, 0, st>>>((const T*)dy, dps, arg, (T*)dx, dxps, accumulate, H, W, C)
-      switch (k) {
-        case 3: MP_LDS(3); break;
-        case 5: MP_LDS(5); break;
-        case 7: MP_LDS(7); break;
-        case 9: MP_LDS(9); break;
-        case 11: MP_LDS(11); break;
-        default: MP_LDS(13); break;
-      }
-#undef MP_LDS
-      return (int)hipGetLastError();
+      return by_int<3, 5, 7, 9, 11, 13>(k, kInvalid, [&](auto ks) {
+        return launch(maxpool_bwd_lds<T, decltype(ks)::value>, gl, stream, dy, dps, arg, dx, dxps, accumulate, H, W, C);
+      });
     });
   }
   return by_dtype_vec(dtype, v, kInvalid, [&](auto tag, auto nv) {
     using T = typename decltype(tag)::type;
     constexpr int NV = decltype(nv)::value;
-    return launch(maxpool_bwd_kernel<T, NV>, vgrid((long)N * H * W * C / NV), st, dy, dps, arg, dx, dxps, accumulate, N,
+    return launch(maxpool_bwd_kernel<T, NV>, vgrid((long)N * H * W * C / NV), stream, dy, dps, arg, dx, dxps, accumulate, N,
         H, W, C, k);
   });
 }
@@ -1423,15 +1392,14 @@ DMY_API long dmy_gpool_ws_bytes(int dtype, int N, int HW, int C) {
 }
 DMY_API int dmy_gpool_fwd(int dtype, const void* x, long xps, int N, int HW, int C, void* out, int* arg, float* ws,
                           void* stream) {
-  hipStream_t st = (hipStream_t)stream;
   const bool v = vec_ok(vec_width(dtype), C, {xps}, {}, {x});
-  const GPoolPlan pl(N, HW, C, v ? vec_width(dtype) : 1);
   return by_dtype_vec(dtype, v, kInvalid, [&](auto tag, auto nv) {
     using T = typename decltype(tag)::type;
     constexpr int NV = decltype(nv)::value;
-    gpool_part_kernel<T, NV><<<dim3(pl.S, N, pl.groups), 256, 0, st>>>((const T*)x, xps, N, HW, C, pl.L, pl.chunk, ws);
-    gpool_final_kernel<T><<<vgrid((long)N * C), 256, 0, st>>>(ws, pl.S, N, HW, C, (T*)out, arg);
-    return (int)hipGetLastError();
+    const GPoolPlan pl(N, HW, C, NV);
+    if (int e = launch(gpool_part_kernel<T, NV>, dim3(pl.S, N, pl.groups), stream, x, xps, N, HW, C, pl.L, pl.chunk, ws))
+      return e;
+    return launch(gpool_final_kernel<T>, vgrid((long)N * C), stream, ws, pl.S, N, HW, C, out, arg);
   });
 }
 DMY_API int dmy_gpool_bwd(int dtype, const void* dz, const int* arg, void* dx, long dxps, int accumulate, int N, int HW,
@@ -1467,18 +1435,16 @@ DMY_API long dmy_cbam_in_bwd_ws_elems(int N, int HW, int C) {
 DMY_API int dmy_cbam_in_bwd(int dtype, const void* x, long xps, const void* ca, const void* dout1, long dps,
                             const void* ds2, const int* am, int N, int HW, int C, void* dx, long dxps, int accumulate,
                             float* dca, float* ws, void* stream) {
-  hipStream_t st = (hipStream_t)stream;
   const bool v = vec_ok(vec_width(dtype), C, {xps, dps, dxps}, {}, {x, ca, dout1, dx});
   const int wpi = (int)ceil_div((long)HW, kCbamPpw);
   const long waves = (long)N * wpi;
   return by_dtype_vec(dtype, v, kInvalid, [&](auto tag, auto nv) {
     using T = typename decltype(tag)::type;
     constexpr int NV = decltype(nv)::value;
-    cbam_in_bwd_kernel<T, NV><<<(unsigned)ceil_div(waves, 4), 256, 0, st>>>(
-        (const T*)x, xps, (const T*)ca, (const T*)dout1, dps, (const T*)ds2, am, N, HW, C, kCbamPpw, wpi, (T*)dx, dxps,
-        accumulate, ws);
-    cbam_fold_kernel<<<grid_cap(ceil_div((long)N * C, 256)), 256, 0, st>>>(ws, N, C, wpi, dca);
-    return (int)hipGetLastError();
+    if (int e = launch(cbam_in_bwd_kernel<T, NV>, (unsigned)ceil_div(waves, 4), stream, x, xps, ca, dout1, dps, ds2, am, N,
+                       HW, C, kCbamPpw, wpi, dx, dxps, accumulate, ws))
+      return e;
+    return launch(cbam_fold_kernel, grid_cap(ceil_div((long)N * C, 256)), stream, ws, N, C, wpi, dca);
   });
 }
 DMY_API int dmy_pixscale(int dtype, const void* out1, const void* sa, long sps, int N, int HW, int C, void* out, long ops,
@@ -1496,15 +1462,10 @@ DMY_API int dmy_slice_copy(int dtype, const void* src, long sps, void* dst, long
   const int VW = vec_width(dtype);
   const bool vec = vec_ok(VW, C, {sps, dps}, {}, {src, dst});
   const long work = M * (vec ? C / VW : C);
-  return by_dtype(dtype, kInvalid, [&](auto tag) {
+  return by_dtype_vec(dtype, vec, kInvalid, [&](auto tag, auto nv) {
     using T = typename decltype(tag)::type;
-    auto launch = [&](auto vt) {
-      slice_copy_kernel<T, decltype(vt)::value><<<vgrid(work), 256, 0, (hipStream_t)stream>>>(
-          (const T*)src, sps, (T*)dst, dps, M, C, wv, idx, nw, eps, accumulate);
-    };
-    if (vec) launch(std::true_type{});
-    else launch(std::false_type{});
-    return (int)hipGetLastError();
+    return launch(slice_copy_kernel<T, (decltype(nv)::value > 1)>, vgrid(work), stream, src, sps, dst, dps, M, C, wv, idx,
+                  nw, eps, accumulate);
   });
 }
 DMY_API int dmy_dot_partial_blocks(long M, int C) { return grid_cap(ceil_div(M * C, 256 * 64), 2048); }
@@ -1530,8 +1491,7 @@ DMY_API int dmy_slice_copy_dot(int dtype, const void* dy, long dps, void* g, lon
   });
 }
 DMY_API int dmy_bifpn_wgrad(const float* part, int nblk, int nw, const float* wv, float eps, float* dw, void* stream) {
-  bifpn_wgrad_kernel<<<1, 64, 0, (hipStream_t)stream>>>(part, nblk, nw, wv, eps, dw);
-  return (int)hipGetLastError();
+  return launch(bifpn_wgrad_kernel, 1, 64, 0, stream, part, nblk, nw, wv, eps, dw);
 }
 DMY_API int dmy_scgate_fwd(int dtype, const void* x, long xps, const void* u3, const void* g, void* out, int N, int H,
                            int W, int C, int GH, int GW, void* stream) {
@@ -1577,14 +1537,13 @@ DMY_API int dmy_ca_apply_fwd(int dtype, const void* x, long xps, const void* lh,
 DMY_API int dmy_ca_apply_bwd(int dtype, const void* x, long xps, const void* lh, const void* lw, const void* dout,
                              long dps, void* dx, long dxps, void* dlh, void* dlw, int N, int H, int W, int C,
                              void* stream) {
-  hipStream_t st = (hipStream_t)stream;
   return by_dtype(dtype, kInvalid, [&](auto tag) {
     using T = typename decltype(tag)::type;
-    ca_apply_bwd_dx_kernel<T><<<vgrid((long)N * H * W * C), 256, 0, st>>>(
-        (const T*)x, xps, (const T*)lh, (const T*)lw, (const T*)dout, dps, (T*)dx, dxps, N, H, W, C);
-    ca_apply_bwd_att_kernel<T><<<vgrid((long)N * (H + W) * C), 256, 0, st>>>(
-        (const T*)x, xps, (const T*)lh, (const T*)lw, (const T*)dout, dps, (T*)dlh, (T*)dlw, N, H, W, C);
-    return (int)hipGetLastError();
+    if (int e = launch(ca_apply_bwd_dx_kernel<T>, vgrid((long)N * H * W * C), stream, x, xps, lh, lw, dout, dps, dx, dxps,
+                       N, H, W, C))
+      return e;
+    return launch(ca_apply_bwd_att_kernel<T>, vgrid((long)N * (H + W) * C), stream, x, xps, lh, lw, dout, dps, dlh, dlw,
+                  N, H, W, C);
   });
 }
 // NCHW image (uint8 or fp32, H and W even) -> space-to-depth NHWC [N][H/2][W/2][Cs] T, channel
@@ -1628,9 +1587,8 @@ DMY_API int dmy_image_s2d(int dtype, int src_kind, const void* x, void* y, int N
   const int g = vgrid((long)N * (H / 2) * (W / 2));
   return by_dtype(dtype, kInvalid, [&](auto tag) {
     using T = typename decltype(tag)::type;
-    if (src_kind == 0) image_s2d_kernel<uint8_t, T><<<g, 256, 0, (hipStream_t)stream>>>((const uint8_t*)x, (T*)y, N, C, H, W, Cs, scale);
-    else image_s2d_kernel<float, T><<<g, 256, 0, (hipStream_t)stream>>>((const float*)x, (T*)y, N, C, H, W, Cs, scale);
-    return (int)hipGetLastError();
+    if (src_kind == 0) return launch(image_s2d_kernel<uint8_t, T>, g, stream, x, y, N, C, H, W, Cs, scale);
+    return launch(image_s2d_kernel<float, T>, g, stream, x, y, N, C, H, W, Cs, scale);
   });
 }
 // src_kind: 0 = uint8, 1 = fp32; output NHWC with pixel stride Cp >= C (zero-filled tail channels).  Cp must be a
@@ -1642,9 +1600,8 @@ DMY_API int dmy_nchw_to_nhwc(int dtype, int src_kind, const void* x, void* y, in
   const int g = vgrid((long)N * H * W);
   return by_dtype(dtype, kInvalid, [&](auto tag) {
     using T = typename decltype(tag)::type;
-    if (src_kind == 0) nchw_to_nhwc_kernel<uint8_t, T><<<g, 256, 0, (hipStream_t)stream>>>((const uint8_t*)x, (T*)y, N, C, H, W, Cp, scale);
-    else nchw_to_nhwc_kernel<float, T><<<g, 256, 0, (hipStream_t)stream>>>((const float*)x, (T*)y, N, C, H, W, Cp, scale);
-    return (int)hipGetLastError();
+    if (src_kind == 0) return launch(nchw_to_nhwc_kernel<uint8_t, T>, g, stream, x, y, N, C, H, W, Cp, scale);
+    return launch(nchw_to_nhwc_kernel<float, T>, g, stream, x, y, N, C, H, W, Cp, scale);
   });
 }
 DMY_API int dmy_nhwc_to_nchw_f32(int dtype, const void* x, long xps, float* y, int N, int C, int H, int W,
@@ -1661,13 +1618,11 @@ DMY_API int dmy_pointwise(int dtype, int op, int act, const void* a, const void*
     return launch(pointwise_kernel<T>, vgrid(n), stream, op, act, a, b, y, n, alpha);
   });
 }
-// kinds: 0 f32, 1 bf16
+// kinds: 0 f32, 1 bf16; any other is refused
 DMY_API int dmy_cast(int src_kind, int dst_kind, const void* x, void* y, long n, float scale, void* stream) {
-  hipStream_t st = (hipStream_t)stream;
-  const int g = vgrid(n);
-  if (src_kind == 0 && dst_kind == 1) cast_kernel<float, bf16><<<g, 256, 0, st>>>((const float*)x, (bf16*)y, n, scale);
-  else if (src_kind == 1 && dst_kind == 0) cast_kernel<bf16, float><<<g, 256, 0, st>>>((const bf16*)x, (float*)y, n, scale);
-  else if (src_kind == 0) cast_kernel<float, float><<<g, 256, 0, st>>>((const float*)x, (float*)y, n, scale);
-  else cast_kernel<bf16, bf16><<<g, 256, 0, st>>>((const bf16*)x, (bf16*)y, n, scale);
-  return (int)hipGetLastError();
+  return by_dtype(src_kind, kInvalid, [&](auto s) {
+    return by_dtype(dst_kind, kInvalid, [&](auto d) {
+      return launch(cast_kernel<typename decltype(s)::type, typename decltype(d)::type>, vgrid(n), stream, x, y, n, scale);
+    });
+  });
 }

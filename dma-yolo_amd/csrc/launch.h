@@ -1,5 +1,5 @@
-// Host-side launch glue shared by the streaming NHWC kernel files (one 16-byte channel vector per thread, no MFMA):
-// the storage-type dispatch, the 16-byte vector contract and the launch grids.  Host code only.
+// Host-side launch glue of every kernel file: the dispatch on storage type, runtime bools and compile-time integers,
+// the launch itself, the 16-byte vector contract and the grids of the streaming kernels.  Host code only.
 #pragma once
 #include "common.h"
 #include <initializer_list>
@@ -15,13 +15,14 @@ template <typename F> inline int by_dtype(int dtype, int refuse, F&& f) {
   if (dtype == 1) return f(DType<bf16>{});
   return refuse;
 }
-template <int N> struct Width { static constexpr int value = N; };
+// an int as a lambda argument (read as decltype(n)::value), never as a kernel's template argument
+template <int N> using Int = std::integral_constant<int, N>;
 // by_dtype for a kernel with a scalar twin: f(tag, nv) with decltype(nv)::value = the elements per 16-byte vector
 // when `vec` holds, else 1
 template <typename F> inline int by_dtype_vec(int dtype, bool vec, int refuse, F&& f) {
   return by_dtype(dtype, refuse, [&](auto tag) {
     using T = typename decltype(tag)::type;
-    return vec ? f(tag, Width<Traits<T>::VW>{}) : f(tag, Width<1>{});
+    return vec ? f(tag, Int<Traits<T>::VW>{}) : f(tag, Int<1>{});
   });
 }
 // by_flags(b0[, b1[, b2]], f): f(std::bool_constant<b0>{}, ...), the runtime bools turned into tags whose ::value picks
@@ -32,16 +33,31 @@ template <size_t I = 0, typename Tup, typename... Tag> inline int by_flags_(cons
   else return by_flags_<I + 1>(a, tags..., std::false_type{});
 }
 template <typename... A> inline int by_flags(A&&... a) { return by_flags_(std::forward_as_tuple(a...)); }
+// by_int<3, 5, 7>(v, refuse, f): f(Int<V>{}) for the listed V equal to v, `refuse` for any other v.
+// by_int<3, 5, 7>(v, Int<0>{}, f): the same, with f(Int<0>{}) for any other v: a ladder's `default:` instantiation.
+// f is a generic lambda that returns the entry's int; it is instantiated for the named values only.
+template <int... V, typename F, typename G> inline int by_int_(int v, F&& f, G&& other) {
+  int r = 0;
+  return ((v == V && (r = f(Int<V>{}), true)) || ...) ? r : other();
+}
+template <int... V, typename F> inline int by_int(int v, int refuse, F&& f) {
+  return by_int_<V...>(v, f, [&] { return refuse; });
+}
+template <int... V, int D, typename F> inline int by_int(int v, Int<D> other, F&& f) {
+  return by_int_<V...>(v, f, [&] { return f(other); });
+}
 
 // k<<<grid, block, lds, stream>>>(args...) and the launch status.  Each argument is converted to the kernel's own
 // parameter type, so an entry passes its void pointers as they are: the kernel's signature, not a cast at the call,
-// types them.  The short form is the streaming kernels' 256 threads and no dynamic LDS.
+// types them.  The short form is the streaming kernels' 256 threads and no dynamic LDS.  An entry with several
+// launches chains them, `if (int e = launch(...)) return e;`: a failed launch returns at once and the later ones are
+// not enqueued.  (static: an instantiation the compiler does not inline stays out of the library's exports.)
 template <typename... P, typename... A>
-inline int launch(void (*k)(P...), dim3 grid, dim3 block, size_t lds, void* stream, A... args) {
+static inline int launch(void (*k)(P...), dim3 grid, dim3 block, size_t lds, void* stream, A... args) {
   k<<<grid, block, lds, (hipStream_t)stream>>>(static_cast<P>(args)...);
   return (int)hipGetLastError();
 }
-template <typename... P, typename... A> inline int launch(void (*k)(P...), dim3 grid, void* stream, A... args) {
+template <typename... P, typename... A> static inline int launch(void (*k)(P...), dim3 grid, void* stream, A... args) {
   return launch(k, grid, 256, 0, stream, args...);
 }
 

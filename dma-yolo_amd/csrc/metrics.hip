@@ -13,7 +13,7 @@
 //      for every label, the survivor with the SMALLEST detection index (not the highest IoU: the
 //      re-sort is commented out at val.py:78)
 //   3. correct[d][t] = matched_iou(d) >= iouv[t]
-#include "common.h"
+#include "launch.h"
 
 namespace {
 
@@ -75,7 +75,5 @@ DMY_API int dmy_process_batch(const float* det, const int* det_off, const float*
                               const float* iouv, int T, int* ws_lab, float* ws_iou, int* ws_win,
                               unsigned char* correct, void* stream) {
   if (B <= 0) return 0;
-  process_batch_kernel<<<B, 256, 0, (hipStream_t)stream>>>(det, det_off, lab, lab_off, iouv, T, ws_lab, ws_iou, ws_win,
-                                                           correct);
-  return (int)hipGetLastError();
+  return launch(process_batch_kernel, B, stream, det, det_off, lab, lab_off, iouv, T, ws_lab, ws_iou, ws_win, correct);
 }

@@ -620,11 +620,6 @@ inline bool mfma_ok(int dtype, const MhaGeom& g, std::initializer_list<const voi
   if (dtype != 1 || !(g.d == 32 || g.d == 64 || g.d == 128)) return false;
   return vec_ok(8, g.d, {g.qps, g.kps, g.vps, g.ops}, {}, ps);
 }
-// f(Int<32 / 64 / 128>) for the head dim of an MFMA launch
-template <int N> using Int = std::integral_constant<int, N>;
-template <typename F> inline int by_head_dim(int d, F&& f) {
-  return d == 32 ? f(Int<32>{}) : d == 64 ? f(Int<64>{}) : f(Int<128>{});
-}
 // the generic forward (any head dim <= 128, either dtype): dmy_mha_fwd's scalar path and dmy_mha_fwd_ref
 inline int mha_fwd_any(int dtype, const void* q, const void* k, const void* v, void* o, float* lse2, const MhaGeom& g,
                        void* stream) {
@@ -645,7 +640,7 @@ DMY_API int dmy_mha_fwd(int dtype, const void* q, long qps, const void* k, long 
   if (d <= 0 || d > 128 || nh <= 0) return kInvalid;
   const MhaGeom g{B, L, nh, d, qps, kps, vps, ops, scale};
   if (!mfma_ok(dtype, g, {q, k, v, o})) return mha_fwd_any(dtype, q, k, v, o, lse2, g, stream);
-  return by_head_dim(d, [&](auto D) {
+  return by_int<32, 64, 128>(d, kInvalid, [&](auto D) {  // the head dims mfma_ok admits
     return launch(mha_fwd_mfma<D.value>, dim3(ceil_div(L, 128), nh, B), stream, q, k, v, o, lse2, g);
   });
 }
@@ -663,7 +658,7 @@ DMY_API int dmy_mha_bwd(int dtype, const void* q, long qps, const void* k, long 
     if (rc != 0) return rc;
     if (mfma_ok(dtype, g, {q, k, v, dout, dq, dk, dv})) {
       const dim3 grid(ceil_div(L, 128), nh, B);
-      return by_head_dim(d, [&](auto D) {
+      return by_int<32, 64, 128>(d, kInvalid, [&](auto D) {
         rc = launch(mha_bwd_dq_mfma<D.value>, grid, stream, q, k, v, dout, lse2, Dq, dq, g);
         return rc ? rc : launch(mha_bwd_dkdv_mfma<D.value>, grid, stream, q, k, v, dout, lse2, Dq, dk, dv, g);
       });
@@ -697,8 +692,7 @@ __global__ void dropout_seed_kernel(unsigned long long* state, unsigned long lon
 }
 
 DMY_API int dmy_dropout_seed(unsigned long long* state, unsigned long long* seed, void* stream) {
-  dropout_seed_kernel<<<1, 64, 0, (hipStream_t)stream>>>(state, seed);
-  return (int)hipGetLastError();
+  return launch(dropout_seed_kernel, 1, 64, 0, stream, state, seed);
 }
 
 DMY_API int dmy_dropout(int dtype, const void* x, long xps, void* y, long yps, long M, int C, float p,

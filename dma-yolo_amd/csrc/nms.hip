@@ -10,7 +10,7 @@
 //     explicit round-to-nearest intrinsics so no FMA contraction changes a bit.
 //   * lazy IoU rows: only rows that are KEPT compute IoU against the rest, and the scan stops at
 //     max_det kept rows, so work is O(n * kept) instead of the O(n^2) mask.
-#include "common.h"
+#include "launch.h"
 
 namespace {
 
@@ -318,22 +318,23 @@ DMY_API int dmy_nms_candidates(const float* pred, int nimg, int A, int no, float
                                void* stream) {
   NmsCfg cfg{A, no, no - 5, conf, 0.f, multi, 0, 0, 0, cls_ok};
   dim3 grid(grid_cap(ceil_div(A, 256), 256), nimg);
-  nms_candidates_kernel<<<grid, 256, 0, (hipStream_t)stream>>>(pred, cfg, keys, cap, counts);
-  return (int)hipGetLastError();
+  return launch(nms_candidates_kernel, grid, stream, pred, cfg, keys, cap, counts);
 }
 
 // cap must be a power of two >= 2048; sorts each image's [0, cap) key segment ascending
 DMY_API int dmy_nms_sort(unsigned long long* keys, long cap, const int* counts, int nimg, void* stream) {
-  hipStream_t st = (hipStream_t)stream;
   dim3 gp(grid_cap(ceil_div(cap, 256), 1024), nimg);
-  if (cap > 2048) pad_keys_kernel<<<gp, 256, 0, st>>>(keys, cap, counts, nimg);  // cap 2048: bitonic_local pads
-  dim3 gl((unsigned)(cap / 2048), nimg);
-  bitonic_local_kernel<<<gl, 1024, 0, st>>>(keys, cap, 2, 2048, counts);
-  for (long k = 4096; k <= cap; k <<= 1) {
-    for (long j = k >> 1; j >= 2048; j >>= 1) bitonic_global_kernel<<<gp, 256, 0, st>>>(keys, cap, k, j);
-    bitonic_local_kernel<<<gl, 1024, 0, st>>>(keys, cap, k, k, counts);
+  if (cap > 2048) {  // cap 2048: bitonic_local pads
+    if (int e = launch(pad_keys_kernel, gp, stream, keys, cap, counts, nimg)) return e;
   }
-  return (int)hipGetLastError();
+  dim3 gl((unsigned)(cap / 2048), nimg);
+  if (int e = launch(bitonic_local_kernel, gl, 1024, 0, stream, keys, cap, 2, 2048, counts)) return e;
+  for (long k = 4096; k <= cap; k <<= 1) {
+    for (long j = k >> 1; j >= 2048; j >>= 1)
+      if (int e = launch(bitonic_global_kernel, gp, stream, keys, cap, k, j)) return e;
+    if (int e = launch(bitonic_local_kernel, gl, 1024, 0, stream, keys, cap, k, k, counts)) return e;
+  }
+  return 0;
 }
 
 DMY_API int dmy_nms_greedy(const float* pred, int nimg, int A, int no, float iou, int agnostic, int max_det,
@@ -341,9 +342,7 @@ DMY_API int dmy_nms_greedy(const float* pred, int nimg, int A, int no, float iou
                            float* out, int* nkeep, int* ncand, void* stream) {
   NmsCfg cfg{A, no, no - 5, 0.f, iou, 0, agnostic, max_det, max_nms, nullptr};
   const size_t lds = sizeof(unsigned long long) * (size_t)((max_nms + 63) / 64);
-  nms_greedy_kernel<<<nimg, 1024, lds, (hipStream_t)stream>>>(pred, cfg, keys, cap, counts, boxes, out, nkeep,
-                                                                ncand);
-  return (int)hipGetLastError();
+  return launch(nms_greedy_kernel, nimg, 1024, lds, stream, pred, cfg, keys, cap, counts, boxes, out, nkeep, ncand);
 }
 
 DMY_API int dmy_nms_mask_rows() { return kMaskCap; }
@@ -352,12 +351,10 @@ DMY_API int dmy_nms_mask_rows() { return kMaskCap; }
 DMY_API int dmy_nms_greedy_mask(const float* pred, int nimg, int A, int no, float iou, int agnostic, int max_det,
                                 int max_nms, const unsigned long long* keys, long cap, int* counts, float* boxes,
                                 unsigned long long* mask, float* out, int* nkeep, int* ncand, void* stream) {
-  if (cap > kMaskCap || cap % 64 != 0) return (int)hipErrorInvalidValue;
+  if (cap > kMaskCap || cap % 64 != 0) return kInvalid;
   NmsCfg cfg{A, no, no - 5, 0.f, iou, 0, agnostic, max_det, max_nms, nullptr};
-  hipStream_t st = (hipStream_t)stream;
   (void)boxes;  // the mask kernel makes its boxes from the keys (the lazy path's scratch; kept in the ABI)
-  nms_mask_kernel<<<dim3((unsigned)(cap / 64), (unsigned)(cap / 64), nimg), 64, 0, st>>>(pred, cfg, keys, cap, counts,
-                                                                                          mask);
-  nms_scan_kernel<<<nimg, 64, 0, st>>>(pred, cfg, keys, cap, counts, mask, out, nkeep, ncand);
-  return (int)hipGetLastError();
+  const dim3 gm((unsigned)(cap / 64), (unsigned)(cap / 64), nimg);
+  if (int e = launch(nms_mask_kernel, gm, 64, 0, stream, pred, cfg, keys, cap, counts, mask)) return e;
+  return launch(nms_scan_kernel, nimg, 64, 0, stream, pred, cfg, keys, cap, counts, mask, out, nkeep, ncand);
 }

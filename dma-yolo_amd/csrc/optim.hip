@@ -1,7 +1,7 @@
 // Multi-tensor optimizer / EMA kernels (HBM-bound).  Replaces torch.optim.SGD(nesterov) / Adam as
 // configured by train.py:197-222 and ModelEMA.update (utils/torch_utils.py:329-339).
 // One launch per parameter group: blocks walk a (tensor, chunk) table built on the host.
-#include "common.h"
+#include "launch.h"
 
 namespace {
 
@@ -135,14 +135,12 @@ DMY_API int dmy_amp_check(const float* const* g, const long* n, const int* tid, 
                           const float* scale, float* found, void* stream) {
   if (nchunks == 0) return 0;
   TList L{nullptr, g, nullptr, nullptr, n, tid, off};
-  amp_check_kernel<<<nchunks, 256, 0, (hipStream_t)stream>>>(L, scale, found);
-  return (int)hipGetLastError();
+  return launch(amp_check_kernel, nchunks, stream, L, scale, found);
 }
 
 DMY_API int dmy_amp_update(float* scale, float* gup, int* tracker, float* found, float world, float growth,
                            float backoff, int interval, void* stream) {
-  amp_update_kernel<<<1, 64, 0, (hipStream_t)stream>>>(scale, gup, tracker, found, world, growth, backoff, interval);
-  return (int)hipGetLastError();
+  return launch(amp_update_kernel, 1, 64, 0, stream, scale, gup, tracker, found, world, growth, backoff, interval);
 }
 
 DMY_API int dmy_sgd(float* const* p, const float* const* g, float* const* m, const long* n, const int* tid,
@@ -150,8 +148,7 @@ DMY_API int dmy_sgd(float* const* p, const float* const* g, float* const* m, con
                     const float* found, void* stream) {
   if (nchunks == 0) return 0;
   TList L{p, g, m, nullptr, n, tid, off};
-  sgd_kernel<<<nchunks, 256, 0, (hipStream_t)stream>>>(L, lr, mom, wd, nesterov, scale, found);
-  return (int)hipGetLastError();
+  return launch(sgd_kernel, nchunks, stream, L, lr, mom, wd, nesterov, scale, found);
 }
 
 DMY_API int dmy_adam(float* const* p, const float* const* g, float* const* m, float* const* v, const long* n,
@@ -159,15 +156,13 @@ DMY_API int dmy_adam(float* const* p, const float* const* g, float* const* m, fl
                      float bc1, float bc2s, const float* scale, const float* found, int* dstep, void* stream) {
   if (nchunks == 0) return 0;
   TList L{p, g, m, v, n, tid, off};
-  adam_kernel<<<nchunks, 256, 0, (hipStream_t)stream>>>(L, lr, b1, b2, eps, wd, bc1, bc2s, scale, found, dstep);
-  if (dstep != nullptr) adam_step_kernel<<<1, 64, 0, (hipStream_t)stream>>>(dstep, found);
-  return (int)hipGetLastError();
+  if (int e = launch(adam_kernel, nchunks, stream, L, lr, b1, b2, eps, wd, bc1, bc2s, scale, found, dstep)) return e;
+  return dstep != nullptr ? launch(adam_step_kernel, 1, 64, 0, stream, dstep, found) : 0;
 }
 
 DMY_API int dmy_ema(float* const* e, const float* const* s, const long* n, const int* tid, const long* off,
                     int nchunks, float d, void* stream) {
   if (nchunks == 0) return 0;
   TList L{e, s, nullptr, nullptr, n, tid, off};
-  ema_kernel<<<nchunks, 256, 0, (hipStream_t)stream>>>(L, d);
-  return (int)hipGetLastError();
+  return launch(ema_kernel, nchunks, stream, L, d);
 }

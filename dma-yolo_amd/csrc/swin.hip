@@ -916,63 +916,40 @@ SwinGeom make(int B, int H, int W, int C, int nh, int shift, float scale) {
 
 }  // namespace
 
-template <typename T>
-int ln_fwd_t(const T* x, long xps, const float* w, const float* b, T* y, float* mean, float* rstd, long M, int C,
-             float eps, hipStream_t st) {
-  const int L = ln_lanes<T>(C, xps, C, x, y);
-  if (L) {
-    const int g = grid_cap(ceil_div(M, 4L * (64 / L)), 8192);
-    switch (L) {
-      case 4: ln_fwd_vec<T, 4><<<g, 256, 0, st>>>(x, xps, w, b, y, mean, rstd, M, C, eps); break;
-      case 8: ln_fwd_vec<T, 8><<<g, 256, 0, st>>>(x, xps, w, b, y, mean, rstd, M, C, eps); break;
-      case 16: ln_fwd_vec<T, 16><<<g, 256, 0, st>>>(x, xps, w, b, y, mean, rstd, M, C, eps); break;
-      case 32: ln_fwd_vec<T, 32><<<g, 256, 0, st>>>(x, xps, w, b, y, mean, rstd, M, C, eps); break;
-      default: ln_fwd_vec<T, 64><<<g, 256, 0, st>>>(x, xps, w, b, y, mean, rstd, M, C, eps); break;
-    }
-  } else {
-    ln_fwd_kernel<T><<<grid_cap(ceil_div(M, 4), 4096), 256, 0, st>>>(x, xps, w, b, y, mean, rstd, M, C, eps);
-  }
-  return (int)hipGetLastError();
-}
-
+// Both LayerNorm entries: the vector kernel of ln_lanes' lane count (4 .. 64), the scalar kernel where it returns 0.
 DMY_API int dmy_layernorm_fwd(int dtype, const void* x, long xps, const float* w, const float* b, void* y, float* mean,
                               float* rstd, long M, int C, float eps, void* stream) {
   return by_dtype(dtype, kInvalid, [&](auto tag) {
     using T = typename decltype(tag)::type;
-    return ln_fwd_t<T>((const T*)x, xps, w, b, (T*)y, mean, rstd, M, C, eps, (hipStream_t)stream);
+    const int L = ln_lanes<T>(C, xps, C, x, y);
+    if (!L) return launch(ln_fwd_kernel<T>, grid_cap(ceil_div(M, 4), 4096), stream, x, xps, w, b, y, mean, rstd, M, C, eps);
+    return by_int<4, 8, 16, 32, 64>(L, kInvalid, [&](auto l) {
+      return launch(ln_fwd_vec<T, decltype(l)::value>, grid_cap(ceil_div(M, 4L * (64 / L)), 8192), stream, x, xps, w, b, y,
+                    mean, rstd, M, C, eps);
+    });
   });
 }
 
 DMY_API int dmy_layernorm_bwd_blocks(long M) { return grid_cap(ceil_div(M, 64), 1024); }
-
-template <typename T>
-int ln_bwd_t(const T* x, long xps, const T* dy, long dps, const float* w, const float* mean, const float* rstd, T* dx,
-             long dxps, int acc, long M, int C, float* pdw, float* pdb, hipStream_t st) {
-  const int P = dmy_layernorm_bwd_blocks(M);
-  const size_t lds = 4 * 2 * sizeof(float) * C;  // [4 waves][2][C]
-  int L = ln_lanes<T>(C, xps, dxps, x, dx);
-  if (L && !vec_ok(Traits<T>::VW, C, {dps}, {}, {dy})) L = 0;
-  switch (L) {
-    case 4: ln_bwd_vec<T, 4><<<P, 256, lds, st>>>(x, xps, dy, dps, w, mean, rstd, dx, dxps, acc, M, C, pdw, pdb); break;
-    case 8: ln_bwd_vec<T, 8><<<P, 256, lds, st>>>(x, xps, dy, dps, w, mean, rstd, dx, dxps, acc, M, C, pdw, pdb); break;
-    case 16: ln_bwd_vec<T, 16><<<P, 256, lds, st>>>(x, xps, dy, dps, w, mean, rstd, dx, dxps, acc, M, C, pdw, pdb); break;
-    case 32: ln_bwd_vec<T, 32><<<P, 256, lds, st>>>(x, xps, dy, dps, w, mean, rstd, dx, dxps, acc, M, C, pdw, pdb); break;
-    case 64: ln_bwd_vec<T, 64><<<P, 256, lds, st>>>(x, xps, dy, dps, w, mean, rstd, dx, dxps, acc, M, C, pdw, pdb); break;
-    default: {
-      const int rpb = (int)((M + P - 1) / P);
-      ln_bwd_kernel<T><<<P, 256, lds, st>>>(x, xps, dy, dps, w, mean, rstd, dx, dxps, acc, M, C, rpb, pdw, pdb);
-    }
-  }
-  return (int)hipGetLastError();
-}
 
 DMY_API int dmy_layernorm_bwd(int dtype, const void* x, long xps, const void* dy, long dps, const float* w,
                               const float* mean, const float* rstd, void* dx, long dxps, int accumulate, long M, int C,
                               float* pdw, float* pdb, void* stream) {
   return by_dtype(dtype, kInvalid, [&](auto tag) {
     using T = typename decltype(tag)::type;
-    return ln_bwd_t<T>((const T*)x, xps, (const T*)dy, dps, w, mean, rstd, (T*)dx, dxps, accumulate, M, C, pdw, pdb,
-                       (hipStream_t)stream);
+    const int P = dmy_layernorm_bwd_blocks(M);
+    const size_t lds = 4 * 2 * sizeof(float) * C;  // [4 waves][2][C]
+    int L = ln_lanes<T>(C, xps, dxps, x, dx);
+    if (L && !vec_ok(Traits<T>::VW, C, {dps}, {}, {dy})) L = 0;
+    if (!L) {
+      const int rpb = (int)((M + P - 1) / P);
+      return launch(ln_bwd_kernel<T>, P, 256, lds, stream, x, xps, dy, dps, w, mean, rstd, dx, dxps, accumulate, M, C, rpb,
+                    pdw, pdb);
+    }
+    return by_int<4, 8, 16, 32, 64>(L, kInvalid, [&](auto l) {
+      return launch(ln_bwd_vec<T, decltype(l)::value>, P, 256, lds, stream, x, xps, dy, dps, w, mean, rstd, dx, dxps,
+                    accumulate, M, C, pdw, pdb);
+    });
   });
 }
 

@@ -514,27 +514,31 @@ DMY_API int dmy_tal_loss(int dtype, const void* box, long sbb, long sbc, long sb
   (void)hipMemsetAsync(amax_o, 0, 4L * B * cap, st);
   (void)hipMemsetAsync(acc, 0, 16, st);
   const float iw = (float)W[0] * stride[0], ih = (float)H[0] * stride[0];
-  if (nt > 0) tal_targets_kernel<<<1, 256, 0, st>>>(targets, nt, B, iw, ih, cap, gt, cnt);
-  else (void)hipMemsetAsync(cnt, 0, 4L * B, st);
-  // one status for the chain, as before: the last error of the launches
+  if (nt > 0) {
+    if (int e = launch(tal_targets_kernel, 1, stream, targets, nt, B, iw, ih, cap, gt, cnt)) return e;
+  } else {
+    (void)hipMemsetAsync(cnt, 0, 4L * B, st);
+  }
+  // the chain stops at its first failed launch
   return by_dtype(dtype, kInvalid, [&](auto tag) {
     using T = typename decltype(tag)::type;
-    const T* bx = (const T*)box;
-    const T* cl = (const T*)cls;
-    tal_decode_kernel<T><<<egrid((long)B * A), 256, 0, st>>>(bx, sbb, sbc, sba, B, A, lt, pbox);
-    tal_topk_kernel<T><<<dim3(cap, B), 256, 0, st>>>(cl, scb, scc, sca, pbox, gt, cnt, B, A, cap, lt, alpha, beta, cand);
-    tal_claim_kernel<<<egrid((long)B * cap * TOPK), 256, 0, st>>>(cand, cnt, B, A, cap, nclaim, owner);
-    tal_resolve_kernel<T><<<egrid((long)B * A), 256, 0, st>>>(cl, scb, scc, sca, pbox, gt, cnt, nclaim, owner, B, A, cap,
-                                                              lt, alpha, beta, metric, amax_m, amax_o);
-    // loss sums: per-block partials folded in block order (deterministic, no float atomics)
     const int nb = egrid((long)B * A);
-    tal_norm_kernel<<<nb, 256, 0, st>>>(owner, metric, amax_m, amax_o, B, A, cap, norm, part);
-    tal_fold_kernel<1><<<1, 256, 0, st>>>(part, nb, acc, 3);
-    tal_loss_kernel<T><<<nb, 256, 0, st>>>(bx, sbb, sbc, sba, cl, scb, scc, sca, gt, owner, norm, B, A, nc, cap, lt,
-                                           pos_weight, acc, part, G);
-    tal_fold_kernel<3><<<1, 256, 0, st>>>(part, nb, acc, 0);
-    tal_finalize_kernel<<<1, 1, 0, st>>>(acc, (float)B, loss, items);
-    return (int)hipGetLastError();
+    if (int e = launch(tal_decode_kernel<T>, nb, stream, box, sbb, sbc, sba, B, A, lt, pbox)) return e;
+    if (int e = launch(tal_topk_kernel<T>, dim3(cap, B), stream, cls, scb, scc, sca, pbox, gt, cnt, B, A, cap, lt, alpha,
+                       beta, cand))
+      return e;
+    if (int e = launch(tal_claim_kernel, egrid((long)B * cap * TOPK), stream, cand, cnt, B, A, cap, nclaim, owner)) return e;
+    if (int e = launch(tal_resolve_kernel<T>, nb, stream, cls, scb, scc, sca, pbox, gt, cnt, nclaim, owner, B, A, cap, lt,
+                       alpha, beta, metric, amax_m, amax_o))
+      return e;
+    // loss sums: per-block partials folded in block order (deterministic, no float atomics)
+    if (int e = launch(tal_norm_kernel, nb, stream, owner, metric, amax_m, amax_o, B, A, cap, norm, part)) return e;
+    if (int e = launch(tal_fold_kernel<1>, 1, stream, part, nb, acc, 3)) return e;
+    if (int e = launch(tal_loss_kernel<T>, nb, stream, box, sbb, sbc, sba, cls, scb, scc, sca, gt, owner, norm, B, A, nc,
+                       cap, lt, pos_weight, acc, part, G))
+      return e;
+    if (int e = launch(tal_fold_kernel<3>, 1, stream, part, nb, acc, 0)) return e;
+    return launch(tal_finalize_kernel, 1, 1, 0, stream, acc, (float)B, loss, items);
   });
 }
 

@@ -586,3 +586,43 @@ def test_cbam_fns(dtype):
     g1r, dsar, g1a, dsaa = R.pixscale_bwd(o1r, sac.double().view(N, HW), d1c.double().view(N, HW, C))
     check('PixScaleFn_dout1', nhwc(o1.grad).reshape(N, HW, C), g1r, g1a, 4, dtype)
     check('PixScaleFn_dsa', sa.grad.reshape(N, HW), dsar, dsaa, C + 1, dtype)
+
+
+# ---------------------------------------------------------------- slice copy and the image source kinds
+@pytest.mark.parametrize('dtype', DTYPES)
+@pytest.mark.parametrize('C,Ct,off', LAYOUTS)
+@pytest.mark.parametrize('acc', [0, 1])
+def test_slice_copy(acc, C, Ct, off, dtype):
+    """dst (+)= src * w[idx] / (sum w + eps) between channel slices of wider buffers, in the vector and the scalar form
+    (LAYOUTS).  The scale is three fp32 additions and a division, then one product and one sum per element: n = 8."""
+    call, ptr, stream = _lib()
+    M, eps = 37, 1e-4
+    gen = gen_for(C, Ct, off, acc)
+    sc_, g0 = randn((M, C), gen, dtype), randn((M, C), gen, dtype)
+    w = torch.rand(3, generator=gen) + 0.5
+    sbuf, src = slab(sc_, Ct, off)
+    dbuf, dst = slab(g0, Ct, off)
+    wd = w.cuda()
+    call('dmy_slice_copy', dcode(dtype), ptr(src), Ct, ptr(dst), Ct, M, C, ptr(wd), 1, 3, eps, acc, stream())
+    t = sc_.double() * (w[1].double() / (w.double().sum() + eps))
+    base = g0.double() * acc
+    check(f'slice_copy_acc{acc}', dst, t + base, t.abs() + base.abs(), 8, dtype)
+    assert untouched(dbuf, off, C) and untouched(sbuf, off, C)
+
+
+@pytest.mark.parametrize('dtype', DTYPES)
+def test_image_s2d_source_kinds(dtype):
+    """dmy_image_s2d reads a uint8 or an fp32 NCHW image: both convert to fp32 exactly before the one product with
+    `scale`, so the two give the same bits; the layout is that of the reference's space-to-depth cat, zero padded"""
+    call, ptr, stream = _lib()
+    N, C, H, W, Cs, scale = 2, 3, 6, 10, 16, 1 / 255
+    x8 = torch.randint(0, 256, (N, C, H, W), generator=gen_for(C, H), dtype=torch.uint8).cuda()
+    outs = []
+    for kind, x in ((0, x8), (1, x8.float())):
+        y = torch.full((N, H // 2, W // 2, Cs), FILL, dtype=dtype, device='cuda')
+        call('dmy_image_s2d', dcode(dtype), kind, ptr(x), ptr(y), N, C, H, W, Cs, scale, stream())
+        outs.append(y)
+    assert torch.equal(outs[0], outs[1])
+    xf = (x8.float() * torch.tensor(scale, dtype=torch.float32)).to(dtype)
+    cat = torch.cat([xf[..., dy::2, dx::2] for dy in (0, 1) for dx in (0, 1)], 1).permute(0, 2, 3, 1)
+    assert torch.equal(outs[0][..., :4 * C], cat) and bool((outs[0][..., 4 * C:] == 0).all())

@@ -82,6 +82,23 @@ def test_layernorm(C, M, eps, dtype):
 
 
 @pytest.mark.parametrize('dtype', DTYPES)
+@pytest.mark.parametrize('lanes', [4, 8, 16, 32, 64, 128])
+def test_layernorm_every_lane_count(lanes, dtype):
+    """C = lanes x one 16-byte vector, M = 7 rows: each lane count the vector kernels are built for (4 .. 64) in each
+    storage type, and 128 lanes, which they refuse, so the scalar kernels run"""
+    C, M, eps = lanes * (8 if dtype == BF16 else 4), 7, 1e-5
+    gen = gen_for(C, M, lanes)
+    Ct, off = C + 8, 8
+    xc = (torch.randn((M, C), generator=gen) * 0.7 + 0.3).to(dtype)
+    dyc = randn((M, C), gen, dtype)
+    xbuf, x = slab(xc, Ct, off)
+    wc, bc, w, b = params(C, gen, True)
+    mean, rstd = run_fwd(xc, x, Ct, wc, bc, w, b, eps, dtype, f'_lanes{lanes}')
+    run_bwd(xc, x, Ct, dyc, wc, w, mean, rstd, dtype, Ct, off, f'_lanes{lanes}')
+    assert untouched(xbuf, off, C)
+
+
+@pytest.mark.parametrize('dtype', DTYPES)
 @pytest.mark.parametrize('off', [8, 3])
 def test_layernorm_many_rows(off, dtype):
     """M = 70 000 rows of 32 channels: the backward's 1024-block cap and both kernels' grid-stride loops; a slice at a

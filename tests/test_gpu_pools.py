@@ -30,6 +30,26 @@ def _grid_values(shape, gen, levels=7):
 @pytest.mark.parametrize('k', [3, 5, 7, 9, 11, 13])
 @pytest.mark.parametrize('N,C,H,W,extra', [(2, 16, 37, 53, 0), (1, 6, 19, 23, 0), (2, 8, 40, 33, 8)])
 def test_maxpool_vs_aten(dtype, k, N, C, H, W, extra):
+    _maxpool_vs_aten(dtype, k, N, C, H, W, extra)
+
+
+@pytest.mark.parametrize('dtype', [torch.bfloat16, torch.float32])
+@pytest.mark.parametrize('k', [3, 5, 7, 9, 11, 13, 15])
+@pytest.mark.parametrize('C', [8, 3])
+def test_maxpool_every_window(dtype, k, C):
+    """every window the entries admit on a 2 x C x 5 x 7 map, smaller than the larger windows: C = 8 is whole 16-byte
+    vectors (the LDS kernels for k <= 13), C = 3 the scalar kernels with their compile-time windows, and k = 15 the
+    runtime-window kernel and the per-pixel backward in both forms"""
+    _maxpool_vs_aten(dtype, k, 2, C, 5, 7, 0)
+
+
+def test_maxpool_vector_kernel_with_compile_time_window():
+    """65536 channel vectors: past the LDS kernels' grid limit, so the 16-byte per-pixel kernels run, forward with
+    the compile-time 5 x 5 window"""
+    _maxpool_vs_aten(torch.bfloat16, 5, 2, 8 * 32768, 3, 4, 0)
+
+
+def _maxpool_vs_aten(dtype, k, N, C, H, W, extra):
     call, ptr, stream = _lib()
     gen = torch.Generator().manual_seed(k * 100 + C)
     dt = 1 if dtype == torch.bfloat16 else 0
