@@ -188,6 +188,7 @@ SIGNATURES = {
     'dmy_wbf': [P, P, P, P, I, I, I, D, D, P, P, P, P],
     # metrics.hip
     'dmy_process_batch': [P, P, P, P, I, P, I, P, P, P, P, P],
+    'dmy_confusion_matrix': [P, P, P, P, I, I, F, F, P, P, P, P, P, P],
     # swin.hip
     'dmy_layernorm_fwd': [I, P, L, P, P, P, P, P, L, I, F, P],
     'dmy_layernorm_bwd_blocks': [L],

@@ -3,16 +3,32 @@ and the per-class AP integration on the host, as the reference does it.
 
   process_batch        val.py:62-83 (+ box_iou utils/metrics.py:254-276)  -> dmy_process_batch (HIP)
   process_batch_multi  the same for a whole batch of images in one launch
+  ConfusionMatrix      utils/metrics.py:114-189 (its own class-agnostic matching)  -> dmy_confusion_matrix (HIP)
   ap_per_class         utils/metrics.py:21-87   (numpy on the host, like the reference: a few thousand
   compute_ap           utils/metrics.py:90-116   scalars per validation run, not a device workload)
   fitness              utils/metrics.py:15-18
 """
+import warnings
+from pathlib import Path
+
 import numpy as np
 import torch
 
 from .._lib import call, ptr, stream
 
 _trapz = getattr(np, 'trapezoid', None) or np.trapz  # numpy 2 renamed trapz (same rule)
+
+
+def _pack(detections, labels, dev):
+    """lists of [n_i, 6] detections and [m_i, 5] labels -> (det [ND, 6], lab [NL, 5], det_off, lab_off [B + 1] int32,
+    n_i list): the packed batch of the matching kernels, fp32 and contiguous on `dev`"""
+    assert len(detections) == len(labels)
+    nd = [int(d.shape[0]) for d in detections]
+    nl = [int(l.shape[0]) for l in labels]
+    det = (torch.cat([d[:, :6].float() for d in detections]) if sum(nd) else torch.zeros(0, 6, device=dev)).contiguous()
+    lab = (torch.cat([l[:, :5].float() for l in labels]) if sum(nl) else torch.zeros(0, 5, device=dev)).contiguous()
+    offs = torch.tensor(np.concatenate([[0], np.cumsum(nd), [0], np.cumsum(nl)]).astype(np.int32)).to(dev)
+    return det, lab, offs[:len(nd) + 1], offs[len(nd) + 1:], nd
 
 
 def process_batch_multi(detections, labels, iouv):
@@ -23,15 +39,10 @@ def process_batch_multi(detections, labels, iouv):
     if dev.type != 'cuda':
         raise RuntimeError('process_batch runs on the gfx950 kernel: tensors must be on a GPU')
     T = iouv.numel()
-    nd = [int(d.shape[0]) for d in detections]
-    nl = [int(l.shape[0]) for l in labels]
-    ND = sum(nd)
-    if ND == 0:
+    if sum(int(d.shape[0]) for d in detections) == 0:
         return [torch.zeros(0, T, dtype=torch.bool, device=dev) for _ in detections]
-    det = torch.cat([d[:, :6].float() for d in detections]).contiguous()
-    lab = (torch.cat([l[:, :5].float() for l in labels]) if sum(nl) else torch.zeros(0, 5, device=dev)).contiguous()
-    offs = torch.tensor(np.concatenate([[0], np.cumsum(nd), [0], np.cumsum(nl)]).astype(np.int32)).to(dev)
-    doff, loff = offs[:len(nd) + 1], offs[len(nd) + 1:]
+    det, lab, doff, loff, nd = _pack(detections, labels, dev)
+    ND = det.shape[0]
     iv = iouv.float().contiguous()
     ws_lab = torch.empty(ND, dtype=torch.int32, device=dev)
     ws_iou = torch.empty(ND, dtype=torch.float32, device=dev)
@@ -45,6 +56,89 @@ def process_batch_multi(detections, labels, iouv):
 def process_batch(detections, labels, iouv):
     """val.py:62-83: correct [N, len(iouv)] for one image (detections [N, 6], labels [M, 5], xyxy)."""
     return process_batch_multi([detections], [labels], iouv)[0]
+
+
+class ConfusionMatrix:
+    """utils/metrics.py:114-189 with the matching on the GPU (csrc/metrics.hip states the rules): rows are predicted
+    classes, columns true classes, index nc is background.  The counters live on the device of the first batch and
+    are only added to there; `.matrix` reads them back, which is the one host synchronisation."""
+
+    def __init__(self, nc, conf=0.25, iou_thres=0.45):
+        self.nc = nc  # number of classes
+        self.conf = conf
+        self.iou_thres = iou_thres
+        self._counts = None  # [nc + 1, nc + 1] int64 on the GPU, made by the first batch
+
+    @property
+    def matrix(self):
+        """the (nc + 1, nc + 1) float64 array the reference keeps, read back from the device"""
+        if self._counts is None:
+            return np.zeros((self.nc + 1, self.nc + 1))
+        return self._counts.cpu().numpy().astype(np.float64)
+
+    def process_batch_multi(self, detections, labels):
+        """detections: list of [n_i, 6] (x1, y1, x2, y2, conf, cls); labels: list of [m_i, 5] (cls, x1, y1, x2, y2),
+        one entry per image, all on one GPU: utils/metrics.py:122-160 for every image in one launch.  Returns None;
+        nothing is read back."""
+        assert len(detections) == len(labels)
+        if not len(detections):
+            return
+        dev = detections[0].device
+        if dev.type != 'cuda':
+            raise RuntimeError('ConfusionMatrix runs on the gfx950 kernel: tensors must be on a GPU')
+        if self._counts is None:
+            self._counts = torch.zeros((self.nc + 1, self.nc + 1), dtype=torch.int64, device=dev)
+        elif self._counts.device != dev:
+            raise RuntimeError(f'ConfusionMatrix counts on {self._counts.device}, batch on {dev}')
+        det, lab, doff, loff, nd = _pack(detections, labels, dev)
+        ND, NL = det.shape[0], lab.shape[0]
+        if NL == 0:
+            return  # without labels nothing is counted (an image's detections count only once one of them matched)
+        ws_lab = torch.empty(max(ND, 1), dtype=torch.int32, device=dev)
+        ws_iou = torch.empty(max(ND, 1), dtype=torch.float32, device=dev)
+        ws_win = torch.empty(max(ND, 1), dtype=torch.int32, device=dev)
+        ws_lab_win = torch.empty(NL, dtype=torch.int32, device=dev)
+        call('dmy_confusion_matrix', ptr(det), ptr(doff), ptr(lab), ptr(loff), len(nd), self.nc, self.conf,
+             self.iou_thres, ptr(ws_lab), ptr(ws_iou), ptr(ws_win), ptr(ws_lab_win), ptr(self._counts), stream())
+
+    def process_batch(self, detections, labels):
+        """utils/metrics.py:122-160 for one image: detections [N, 6], labels [M, 5], xyxy.  Returns None."""
+        self.process_batch_multi([detections], [labels])
+
+    def plot(self, normalize=True, save_dir='', names=()):
+        """utils/metrics.py:165-185: the heatmap of the (column-normalised) matrix, written to
+        save_dir/confusion_matrix.png.  Cells under 0.005 are left blank, cell values are annotated below 30
+        classes, the tick labels are `names` + background when there is one name per class (fewer than 99).
+        Any failure, a missing plotting library included, is a printed warning and not an error."""
+        try:
+            import matplotlib.pyplot as plt
+            import seaborn as sn
+
+            array = self.matrix
+            if normalize:
+                array = array / (array.sum(0, keepdims=True) + 1e-6)
+            array[array < 0.005] = np.nan
+            named = 0 < len(names) < 99 and len(names) == self.nc
+            xticks = list(names) + ['background FP'] if named else 'auto'
+            yticks = list(names) + ['background FN'] if named else 'auto'
+            fig = plt.figure(figsize=(12, 9), tight_layout=True)
+            sn.set(font_scale=0.8 if self.nc >= 50 else 1.0)
+            with warnings.catch_warnings():
+                warnings.simplefilter('ignore')  # an all-NaN (empty) matrix warns
+                ax = sn.heatmap(array, annot=self.nc < 30, annot_kws={'size': 8}, fmt='.2f', cmap='Blues', square=True,
+                                xticklabels=xticks, yticklabels=yticks)
+            ax.set_facecolor((1, 1, 1))
+            ax.set_xlabel('True')
+            ax.set_ylabel('Predicted')
+            fig.savefig(Path(save_dir) / 'confusion_matrix.png', dpi=250)
+            plt.close()
+        except Exception as e:
+            print(f'WARNING: ConfusionMatrix plot failure: {e}')
+
+    def print(self):
+        """utils/metrics.py:187-189: one line per row, the values separated by blanks"""
+        for row in self.matrix:
+            print(' '.join(str(v) for v in row))
 
 
 def compute_ap(recall, precision):

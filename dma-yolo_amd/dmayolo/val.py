@@ -13,7 +13,11 @@ Multi-model ensembles (the reference's val2.py per model -> txt -> wbf.py chain,
 models plus wbf=dict(iou_thr, skip_box_thr, weights).  Each batch goes through every model and its own NMS, the padded
 NMS buffers are fused on the device by weighted boxes fusion over the network-size image (utils/wbf.wbf_padded), and the
 statistics are taken from the fused rows.
-Out of scope (control plane): plots, COCO-JSON, confusion matrix, txt saving.
+
+Confusion matrix (val.py:178, 263-264): run(..., confusion_matrix=utils.metrics.ConfusionMatrix(nc)) feeds the instance
+every batch's native-space (predn, labelsn) pairs in one launch, for the images that have both labels and predictions;
+the caller reads .matrix / calls .plot() afterwards.  Without an instance nothing of it runs.
+Out of scope (control plane): plots, COCO-JSON, txt saving.
 """
 import numpy as np
 import torch
@@ -25,10 +29,12 @@ from .utils.wbf import wbf_padded
 WBF_DEFAULTS = dict(iou_thr=0.67, skip_box_thr=0.01, weights=None)  # wbf.py:33-34
 
 
-def batch_stats(out, targets, img_hw, iouv, shapes=None, single_cls=False):
+def batch_stats(out, targets, img_hw, iouv, shapes=None, single_cls=False, confusion_matrix=None):
     """val.py:236-270 for one batch: NMS outputs `out` (list of [k, 6]), targets [nt, 6] with PIXEL xywh ->
     list of (correct [k, T] bool, conf [k], pcls [k], tcls list) numpy tuples; every image's matching in one
-    process_batch launch."""
+    process_batch launch.  confusion_matrix: a utils.metrics.ConfusionMatrix that takes the same native-space rows
+    of every image with labels AND predictions (val.py:258-264: an image with labels and no predictions adds
+    nothing to it), in one more launch."""
     device, niou = iouv.device, iouv.numel()
     height, width = img_hw
     stats, dets, labs, tcls_all, keep = [], [], [], [], []
@@ -56,6 +62,10 @@ def batch_stats(out, targets, img_hw, iouv, shapes=None, single_cls=False):
         labs.append(labelsn)
         tcls_all.append(tcls)
         keep.append(pred)
+    if confusion_matrix is not None:
+        both = [(d, l) for d, l in zip(dets, labs) if len(l)]
+        if both:
+            confusion_matrix.process_batch_multi(*zip(*both))
     if dets:
         for correct, pred, tcls in zip(process_batch_multi(dets, labs, iouv), keep, tcls_all):
             stats.append((correct.cpu().numpy(), pred[:, 4].float().cpu().numpy(), pred[:, 5].float().cpu().numpy(),
@@ -102,13 +112,15 @@ def fused_detections(outs, img_hw, conf_thres, iou_thres, max_det, single_cls, w
 
 @torch.no_grad()
 def run(model, batches, nc, conf_thres=0.001, iou_thres=0.6, max_det=300, single_cls=False, compute_loss=None,
-        augment=False, wbf=None):
+        augment=False, wbf=None, confusion_matrix=None):
     """Returns ((mp, mr, map50, map, *loss), maps [nc], seen, nt [nc]) like val.py:303-311.  augment: the model's
     test-time-augmented forward (val.py:213); it has no per-level outputs, so it excludes compute_loss.
     model may be a list or tuple of models with wbf=dict(iou_thr=0.67, skip_box_thr=0.01, weights=None) (missing
     entries take these defaults, wbf.py:33-34): every batch goes through each model and its own NMS, and weighted
     boxes fusion over the network-size image makes the rows the statistics see.  The fused path has no per-level
-    outputs either, so it excludes compute_loss."""
+    outputs either, so it excludes compute_loss.
+    confusion_matrix: an optional utils.metrics.ConfusionMatrix, updated in place from every batch (val.py:263-264);
+    the return value does not change."""
     if augment and compute_loss:
         raise ValueError('augment=True returns no per-level outputs for compute_loss (val.py:213-217)')
     many = isinstance(model, (list, tuple))
@@ -154,7 +166,7 @@ def run(model, batches, nc, conf_thres=0.001, iou_thres=0.6, max_det=300, single
                                       max_det=max_det)
         nbatches += 1
         seen += len(out)
-        stats += batch_stats(out, targets, (height, width), iouv, shapes, single_cls)
+        stats += batch_stats(out, targets, (height, width), iouv, shapes, single_cls, confusion_matrix)
     mp, mr, map50, map_, maps, nt = summarize(stats, nc)
     for m, t in zip(models, was_training):
         m.train(t)

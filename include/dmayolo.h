@@ -606,6 +606,16 @@ int dmy_process_batch(const float* det, const int* det_off, const float* lab, co
                       const float* iouv, int T, int* ws_lab, float* ws_iou, int* ws_win, unsigned char* correct,
                       void* stream);
 
+/* ---- confusion matrix: replaces ConfusionMatrix.process_batch (utils/metrics.py:122-160) for a batch of images
+ *      in one launch, over the packed layout of dmy_process_batch.  Only detections with conf > `conf` take
+ *      part; a (label, detection) pair is a candidate when iou > iou_thres (both strict, classes not compared).
+ *      ws_lab / ws_iou / ws_win: ND entries, ws_lab_win: NL entries.  matrix [(nc + 1)][(nc + 1)] 64-bit
+ *      counters, row = predicted class, column = true class, index nc = background; the entry ADDS into it and
+ *      never clears it.  A class outside [0, nc) is not stored.  Matching rules: csrc/metrics.hip header. */
+int dmy_confusion_matrix(const float* det, const int* det_off, const float* lab, const int* lab_off, int B, int nc,
+                         float conf, float iou_thres, int* ws_lab, float* ws_iou, int* ws_win, int* ws_lab_win,
+                         unsigned long long* matrix, void* stream);
+
 /* ---- training augmentation tail (augment.hip): utils/datasets.py:552-622 after the random draws -- warp
  *      (cv2.warpAffine / warpPerspective INTER_LINEAR, border 114), mixup, augment_hsv, flips, BGR->RGB, HWC->CHW --
  *      for n host-built descriptors (984-byte AugDesc: canvas pointers, inverse maps, mixup ratio, HSV LUTs,
