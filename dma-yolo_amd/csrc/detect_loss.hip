@@ -4,7 +4,8 @@
 //  * build_targets: utils/loss.py:220-276, candidate order offset-major -> anchor -> target (the
 //    reference's repeat/mask order), stream-compacted by ONE block per level with a block scan;
 //    gij is clamped before tbox (the reference's in-place clamp_).
-//  * loss: utils/loss.py:167-218 with utils/metrics.py:192-235 (SIoU).  Gradients of SIoU come from
+//  * loss: utils/loss.py:167-218 with utils/metrics.py:192-252 (SIoU, or the CIoU / DIoU / GIoU / plain IoU the
+//    bbox_iou keywords select: iou.h, a compile-time parameter of the target kernel).  Gradients of the IoU come from
 //    forward-mode dual numbers (4 partials: px, py, pw, ph), so they follow the same expression as
 //    the reference autograd graph; torch.minimum/maximum ties split the gradient in half, abs'(0)=0.
 //    tobj keeps the max clamped IoU per cell (sort_obj_iou forced on, loss.py:191-194) via an
@@ -16,7 +17,7 @@
 //    the EX = true instances of the level kernels; the EX = false instances are the plain-BCE path, unchanged.
 // Everything stays on device: target counts are read by the kernels, never by the host.
 #include "launch.h"
-#include "dual.h"
+#include "iou.h"
 
 namespace {
 
@@ -226,36 +227,6 @@ __global__ void __launch_bounds__(1024) build_targets_kernel(const float* __rest
   if (threadIdx.x == 0) *o.count = base;
 }
 
-// SIoU(b1, b2) for xywh boxes, utils/metrics.py:192-235; b1 carries the derivatives
-DEV D4 siou(D4 x1, D4 y1, D4 w1_, D4 h1_, float x2, float y2, float w2_, float h2_) {
-  const float eps = 1e-7f;
-  D4 b1x1 = x1 - scal(w1_, 0.5f), b1x2 = x1 + scal(w1_, 0.5f);
-  D4 b1y1 = y1 - scal(h1_, 0.5f), b1y2 = y1 + scal(h1_, 0.5f);
-  D4 b2x1 = dc(x2 - w2_ / 2), b2x2 = dc(x2 + w2_ / 2);
-  D4 b2y1 = dc(y2 - h2_ / 2), b2y2 = dc(y2 + h2_ / 2);
-  D4 inter = dclamp0(dmin(b1x2, b2x2) - dmax(b1x1, b2x1)) * dclamp0(dmin(b1y2, b2y2) - dmax(b1y1, b2y1));
-  D4 w1 = b1x2 - b1x1, h1 = b1y2 - b1y1 + dc(eps);
-  D4 w2 = b2x2 - b2x1, h2 = b2y2 - b2y1 + dc(eps);
-  D4 uni = w1 * h1 + w2 * h2 - inter + dc(eps);
-  D4 iou = inter / uni;
-  D4 cw = dmax(b1x2, b2x2) - dmin(b1x1, b2x1);
-  D4 ch = dmax(b1y2, b2y2) - dmin(b1y1, b2y1);
-  D4 scw = scal(b2x1 + b2x2 - b1x1 - b1x2, 0.5f);
-  D4 sch = scal(b2y1 + b2y2 - b1y1 - b1y2, 0.5f);
-  D4 sigma = dsqrt(dsq(scw) + dsq(sch));
-  D4 sa1 = dabs(scw) / sigma, sa2 = dabs(sch) / sigma;
-  const float thr = 0.70710678118654757f;  // pow(2, 0.5) / 2 (python double -> fp32 compare)
-  D4 sa = sa1.v > thr ? sa2 : sa1;
-  D4 ang = dcos(scal(dasin(sa), 2.f) - dc(1.5707963267948966f));
-  D4 rx = dsq(scw / cw), ry = dsq(sch / ch);
-  D4 gam = ang - dc(2.f);
-  D4 dist = dc(2.f) - dexp(gam * rx) - dexp(gam * ry);
-  D4 ow = dabs(w1 - w2) / dmax(w1, w2);
-  D4 oh = dabs(h1 - h2) / dmax(h1, h2);
-  D4 shape = dpow4(dc(1.f) - dexp(scal(ow, -1.f))) + dpow4(dc(1.f) - dexp(scal(oh, -1.f)));
-  return iou - scal(dist + shape, 0.5f);
-}
-
 // BCEWithLogits(pos_weight) element and its derivative (ATen formulation)
 DEV float bce(float x, float t, float pw, float* g) {
   const float lw = 1.f + (pw - 1.f) * t;
@@ -316,11 +287,12 @@ struct LossCfg {
 // reduced in a fixed order by loss_finalize_kernel -- no float atomics, so the loss is run-to-run bit-identical.
 constexpr int LOSS_PMAX = 2048;
 
-// per selected target j: SIoU box loss + cls BCE + tobj scatter-max.  The target's gradient contribution to its
+// per selected target j: IoU box loss (KIND: iou.h's criterion, SIoU in the reference's own call at
+// utils/loss.py:185) + cls BCE + tobj scatter-max.  The target's gradient contribution to its
 // cell's box / cls channels goes to tgrad[j][4 + nc] (no atomics), and j is pushed on its cell's list (head / nxt);
 // loss_combine_kernel then sums each cell's contributions in ascending j -- the order of the reference's
 // index_put_(accumulate=True) backward of pi[b, a, gj, gi] (utils/loss.py:179).
-template <typename T, bool EX>
+template <typename T, bool EX, int KIND>
 __global__ void loss_targets_kernel(const T* __restrict__ p, LossCfg cfg, LossEx ex, const int* __restrict__ tb,
                                     const int* __restrict__ ta, const int* __restrict__ tgj, const int* __restrict__ tgi,
                                     const int* __restrict__ tcls, const float* __restrict__ tbox,
@@ -341,7 +313,7 @@ __global__ void loss_targets_kernel(const T* __restrict__ p, LossCfg cfg, LossEx
     const float q2 = sg[2] * 2.f, q3 = sg[3] * 2.f;
     D4 pw = dc((q2 * q2) * anch[j * 2]), ph = dc((q3 * q3) * anch[j * 2 + 1]);
     px.d[0] = 1.f; py.d[1] = 1.f; pw.d[2] = 1.f; ph.d[3] = 1.f;
-    D4 iou = siou(px, py, pw, ph, tbox[j * 4], tbox[j * 4 + 1], tbox[j * 4 + 2], tbox[j * 4 + 3]);
+    D4 iou = bbox_iou_d4<KIND, false>(px, py, pw, ph, tbox[j * 4], tbox[j * 4 + 1], tbox[j * 4 + 2], tbox[j * 4 + 3]);
     lbox += 1.f - iou.v;
     // d(mean(1-iou))/d p_k  scaled by box gain * bs
     const float gs = -cfg.box_gain * cfg.bs / (float)M;
@@ -561,26 +533,67 @@ __global__ void loss_grad_kernel(const float* __restrict__ G, const float* __res
     dp[i] = from_f<T>(G[i] * u);
 }
 
-// one level of the YOLO loss (FOCAL: the focal element and the device-side balance of LossEx): target pass, combine
-// of the per-cell lists, objectness pass
+// one level of the YOLO loss (FOCAL: the focal element and the device-side balance of LossEx; iou_kind: the DMY_IOU_*
+// criterion of the box term, an unknown one is refused before anything is enqueued): target pass, combine of the
+// per-cell lists, objectness pass
 template <bool FOCAL>
-int loss_level(int dtype, const void* p, const LossCfg& cfg, const LossEx& ex, const int* tb, const int* ta,
-               const int* tgj, const int* tgi, const int* tcls, const float* tbox, const float* anch, const int* count,
-               int cap, float* G, float* tobj, float* part, float* tgrad, int* links, void* stream) {
+int loss_level(int dtype, int iou_kind, const void* p, const LossCfg& cfg, const LossEx& ex, const int* tb,
+               const int* ta, const int* tgj, const int* tgi, const int* tcls, const float* tbox, const float* anch,
+               const int* count, int cap, float* G, float* tobj, float* part, float* tgrad, int* links, void* stream) {
   return by_dtype(dtype, kInvalid, [&](auto tag) {
     using T = typename decltype(tag)::type;
-    const int gt = grid_cap(ceil_div(cap, 256), 1024);
-    const long cells = (long)cfg.N * cfg.na * cfg.H * cfg.W;
-    int* head = links;
-    int* nxt = links + cells;
-    (void)hipMemsetAsync(head, 0xff, sizeof(int) * (size_t)cells, (hipStream_t)stream);  // empty lists (-1)
-    int rc = launch(loss_targets_kernel<T, FOCAL>, gt, stream, p, cfg, ex, tb, ta, tgj, tgi, tcls, tbox, anch, count,
-                    tgrad, head, nxt, tobj, part);
-    if (rc == 0) rc = launch(loss_combine_kernel, gt, stream, cfg, tb, ta, tgj, tgi, count, tgrad, head, nxt, G);
-    if (rc != 0) return rc;
-    return launch(loss_obj_kernel<T, FOCAL>, grid_cap(ceil_div(cells, 256), LOSS_PMAX), stream, p, cfg, ex, tobj, G,
-                  part);
+    return by_int<kIouSIoU, kIouCIoU, kIouDIoU, kIouGIoU, kIouPlain>(iou_kind, kInvalid, [&](auto kind) {
+      const int gt = grid_cap(ceil_div(cap, 256), 1024);
+      const long cells = (long)cfg.N * cfg.na * cfg.H * cfg.W;
+      int* head = links;
+      int* nxt = links + cells;
+      (void)hipMemsetAsync(head, 0xff, sizeof(int) * (size_t)cells, (hipStream_t)stream);  // empty lists (-1)
+      int rc = launch(loss_targets_kernel<T, FOCAL, decltype(kind)::value>, gt, stream, p, cfg, ex, tb, ta, tgj, tgi,
+                      tcls, tbox, anch, count, tgrad, head, nxt, tobj, part);
+      if (rc == 0) rc = launch(loss_combine_kernel, gt, stream, cfg, tb, ta, tgj, tgi, count, tgrad, head, nxt, G);
+      if (rc != 0) return rc;
+      return launch(loss_obj_kernel<T, FOCAL>, grid_cap(ceil_div(cells, 256), LOSS_PMAX), stream, p, cfg, ex, tobj, G,
+                    part);
+    });
   });
+}
+
+// what dmy_yolo_loss_level and dmy_yolo_loss_level_iou share, and likewise the two focal entries
+int loss_level_plain(int dtype, int iou_kind, const void* p, long sb, long sa, long sh, long sw, int N, int na, int H,
+                     int W, int no, int nc, float box_gain, float obj_gain, float cls_gain, float cls_pw, float obj_pw,
+                     float cp, float cn, float balance, float bs, const int* tb, const int* ta, const int* tgj,
+                     const int* tgi, const int* tcls, const float* tbox, const float* anch, const int* count, int cap,
+                     float* G, float* tobj, float* part, float* tgrad, int* links, void* stream) {
+  const LossCfg cfg{box_gain, obj_gain, cls_gain, cls_pw, obj_pw, cp, cn, balance, bs, nc, na, no, N, H, W, sb, sa, sh, sw};
+  return loss_level<false>(dtype, iou_kind, p, cfg, LossEx{}, tb, ta, tgj, tgi, tcls, tbox, anch, count, cap, G, tobj,
+                           part, tgrad, links, stream);
+}
+
+int loss_level_focal(int dtype, int iou_kind, const void* p, long sb, long sa, long sh, long sw, int N, int na, int H,
+                     int W, int no, int nc, float box_gain, float obj_gain, float cls_gain, float cls_pw, float obj_pw,
+                     float cp, float cn, const double* balance, int level, float fl_gamma, float bs, const int* tb,
+                     const int* ta, const int* tgj, const int* tgi, const int* tcls, const float* tbox,
+                     const float* anch, const int* count, int cap, float* G, float* tobj, float* part, float* tgrad,
+                     int* links, void* stream) {
+  if (dtype != 0 && dtype != 1) return kInvalid;
+  if (!(fl_gamma >= 0.f) || level < 0 || level >= kBalLevels || balance == nullptr) return kInvalid;
+  const LossCfg cfg{box_gain, obj_gain, cls_gain, cls_pw, obj_pw, cp, cn, 0.f, bs, nc, na, no, N, H, W, sb, sa, sh, sw};
+  const int gmode = fl_gamma == 0.f ? 0 : fl_gamma == 1.f ? 1 : fl_gamma == 1.5f ? 2 : fl_gamma == 2.f ? 3 : 4;
+  return loss_level<true>(dtype, iou_kind, p, cfg, LossEx{balance, level, gmode, fl_gamma}, tb, ta, tgj, tgi, tcls,
+                          tbox, anch, count, cap, G, tobj, part, tgrad, links, stream);
+}
+
+// n box pairs through bbox_iou_d4: value and d(iou)/d(b1), the seeds on b1's four numbers in either form
+template <int KIND, bool XYXY>
+__global__ void bbox_iou_eval_kernel(const float* __restrict__ b1, const float* __restrict__ b2,
+                                     float* __restrict__ iou, float* __restrict__ grad, int n) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  D4 x = dc(b1[i * 4]), y = dc(b1[i * 4 + 1]), w = dc(b1[i * 4 + 2]), h = dc(b1[i * 4 + 3]);
+  x.d[0] = 1.f; y.d[1] = 1.f; w.d[2] = 1.f; h.d[3] = 1.f;
+  const D4 r = bbox_iou_d4<KIND, XYXY>(x, y, w, h, b2[i * 4], b2[i * 4 + 1], b2[i * 4 + 2], b2[i * 4 + 3]);
+  iou[i] = r.v;
+  for (int k = 0; k < 4; ++k) grad[i * 4 + k] = r.d[k];
 }
 
 }  // namespace
@@ -678,9 +691,9 @@ DMY_API int dmy_yolo_loss_level(int dtype, const void* p, long sb, long sa, long
                                 const int* ta, const int* tgj, const int* tgi, const int* tcls, const float* tbox,
                                 const float* anch, const int* count, int cap, float* G, float* tobj, float* part,
                                 float* tgrad, int* links, void* stream) {
-  const LossCfg cfg{box_gain, obj_gain, cls_gain, cls_pw, obj_pw, cp, cn, balance, bs, nc, na, no, N, H, W, sb, sa, sh, sw};
-  return loss_level<false>(dtype, p, cfg, LossEx{}, tb, ta, tgj, tgi, tcls, tbox, anch, count, cap, G, tobj, part, tgrad,
-                           links, stream);
+  return loss_level_plain(dtype, DMY_IOU_SIOU, p, sb, sa, sh, sw, N, na, H, W, no, nc, box_gain, obj_gain, cls_gain,
+                          cls_pw, obj_pw, cp, cn, balance, bs, tb, ta, tgj, tgi, tcls, tbox, anch, count, cap, G, tobj,
+                          part, tgrad, links, stream);
 }
 
 // dmy_yolo_loss_level with the focal element (fl_gamma > 0; 0 = plain BCE) and the balance read from balance[level]
@@ -693,12 +706,35 @@ DMY_API int dmy_yolo_loss_level_focal(int dtype, const void* p, long sb, long sa
                                       const int* tgi, const int* tcls, const float* tbox, const float* anch,
                                       const int* count, int cap, float* G, float* tobj, float* part, float* tgrad,
                                       int* links, void* stream) {
-  if (dtype != 0 && dtype != 1) return kInvalid;
-  if (!(fl_gamma >= 0.f) || level < 0 || level >= kBalLevels || balance == nullptr) return kInvalid;
-  const LossCfg cfg{box_gain, obj_gain, cls_gain, cls_pw, obj_pw, cp, cn, 0.f, bs, nc, na, no, N, H, W, sb, sa, sh, sw};
-  const int gmode = fl_gamma == 0.f ? 0 : fl_gamma == 1.f ? 1 : fl_gamma == 1.5f ? 2 : fl_gamma == 2.f ? 3 : 4;
-  return loss_level<true>(dtype, p, cfg, LossEx{balance, level, gmode, fl_gamma}, tb, ta, tgj, tgi, tcls, tbox, anch,
+  return loss_level_focal(dtype, DMY_IOU_SIOU, p, sb, sa, sh, sw, N, na, H, W, no, nc, box_gain, obj_gain, cls_gain,
+                          cls_pw, obj_pw, cp, cn, balance, level, fl_gamma, bs, tb, ta, tgj, tgi, tcls, tbox, anch,
                           count, cap, G, tobj, part, tgrad, links, stream);
+}
+
+// dmy_yolo_loss_level / dmy_yolo_loss_level_focal with the box criterion chosen: iou_kind is a DMY_IOU_* code, the
+// keyword of the reference's bbox_iou call at utils/loss.py:185 (utils/metrics.py:192-252).  DMY_IOU_SIOU runs the very
+// kernels of the entries above; an unknown kind returns hipErrorInvalidValue and launches nothing.
+DMY_API int dmy_yolo_loss_level_iou(int dtype, const void* p, long sb, long sa, long sh, long sw, int N, int na, int H,
+                                    int W, int no, int nc, float box_gain, float obj_gain, float cls_gain, float cls_pw,
+                                    float obj_pw, float cp, float cn, float balance, float bs, const int* tb,
+                                    const int* ta, const int* tgj, const int* tgi, const int* tcls, const float* tbox,
+                                    const float* anch, const int* count, int cap, float* G, float* tobj, float* part,
+                                    float* tgrad, int* links, void* stream, int iou_kind) {
+  return loss_level_plain(dtype, iou_kind, p, sb, sa, sh, sw, N, na, H, W, no, nc, box_gain, obj_gain, cls_gain, cls_pw,
+                          obj_pw, cp, cn, balance, bs, tb, ta, tgj, tgi, tcls, tbox, anch, count, cap, G, tobj, part,
+                          tgrad, links, stream);
+}
+
+DMY_API int dmy_yolo_loss_level_focal_iou(int dtype, const void* p, long sb, long sa, long sh, long sw, int N, int na,
+                                          int H, int W, int no, int nc, float box_gain, float obj_gain, float cls_gain,
+                                          float cls_pw, float obj_pw, float cp, float cn, const double* balance,
+                                          int level, float fl_gamma, float bs, const int* tb, const int* ta,
+                                          const int* tgj, const int* tgi, const int* tcls, const float* tbox,
+                                          const float* anch, const int* count, int cap, float* G, float* tobj,
+                                          float* part, float* tgrad, int* links, void* stream, int iou_kind) {
+  return loss_level_focal(dtype, iou_kind, p, sb, sa, sh, sw, N, na, H, W, no, nc, box_gain, obj_gain, cls_gain, cls_pw,
+                          obj_pw, cp, cn, balance, level, fl_gamma, bs, tb, ta, tgj, tgi, tcls, tbox, anch, count, cap,
+                          G, tobj, part, tgrad, links, stream);
 }
 
 DMY_API int dmy_yolo_loss_finalize(const float* part, int nl, float box, float obj, float cls, float bs, float* loss,
@@ -720,19 +756,20 @@ DMY_API int dmy_loss_grad(int dtype, const float* G, const float* up, void* dp, 
   });
 }
 
-// SIoU of n xywh box pairs through the loss kernel's own siou(): value and d(iou)/d(b1) (test entry)
-__global__ void siou_eval_kernel(const float* __restrict__ b1, const float* __restrict__ b2, float* __restrict__ iou,
-                                 float* __restrict__ grad, int n) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  D4 x = dc(b1[i * 4]), y = dc(b1[i * 4 + 1]), w = dc(b1[i * 4 + 2]), h = dc(b1[i * 4 + 3]);
-  x.d[0] = 1.f; y.d[1] = 1.f; w.d[2] = 1.f; h.d[3] = 1.f;
-  const D4 r = siou(x, y, w, h, b2[i * 4], b2[i * 4 + 1], b2[i * 4 + 2], b2[i * 4 + 3]);
-  iou[i] = r.v;
-  for (int k = 0; k < 4; ++k) grad[i * 4 + k] = r.d[k];
-}
-
+// SIoU of n xywh box pairs through the loss kernel's own device function: value and d(iou)/d(b1) (test entry)
 DMY_API int dmy_siou_eval(const float* b1, const float* b2, float* iou, float* grad, int n, void* stream) {
   if (n <= 0) return 0;
-  return launch(siou_eval_kernel, ceil_div(n, 256), stream, b1, b2, iou, grad, n);
+  return launch(bbox_iou_eval_kernel<kIouSIoU, false>, ceil_div(n, 256), stream, b1, b2, iou, grad, n);
+}
+
+// any criterion in either input form (xyxy != 0: corners as given): what dmayolo.utils.metrics.bbox_iou runs
+DMY_API int dmy_bbox_iou_eval(int iou_kind, int xyxy, const float* b1, const float* b2, float* iou, float* grad_b1,
+                              int n, void* stream) {
+  return by_int<kIouSIoU, kIouCIoU, kIouDIoU, kIouGIoU, kIouPlain>(iou_kind, kInvalid, [&](auto kind) {
+    if (n <= 0) return 0;
+    return by_flags(xyxy != 0, [&](auto corners) {
+      return launch(bbox_iou_eval_kernel<decltype(kind)::value, decltype(corners)::value>, ceil_div(n, 256), stream, b1,
+                    b2, iou, grad_b1, n);
+    });
+  });
 }

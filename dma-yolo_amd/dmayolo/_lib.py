@@ -156,6 +156,11 @@ SIGNATURES = {
     'dmy_yolo_loss_finalize_balance': [P, I, F, F, F, F, P, I, I, P, P, P],
     'dmy_loss_grad': [I, P, P, P, L, P],
     'dmy_siou_eval': [P, P, P, P, I, P],
+    'dmy_yolo_loss_level_iou': [I, P, L, L, L, L, I, I, I, I, I, I, F, F, F, F, F, F, F, F, F, P, P, P, P, P, P, P, P,
+                                I, P, P, P, P, P, P, I],
+    'dmy_yolo_loss_level_focal_iou': [I, P, L, L, L, L, I, I, I, I, I, I, F, F, F, F, F, F, F, P, I, F, F, P, P, P, P,
+                                      P, P, P, P, I, P, P, P, P, P, P, I],
+    'dmy_bbox_iou_eval': [I, I, P, P, P, P, I, P],
     # tal.hip
     'dmy_tal_workspace_bytes': [I, I, I],
     'dmy_tal_loss': [I, P, L, L, L, P, L, L, L, I, I, I, P, P, P, P, I, F, F, F, P, P, P, P, P],
@@ -208,6 +213,10 @@ KERN = {n: i for i, n in enumerate(
      'V2_BIG', 'S2_Q2S', 'S2_Q2', 'S2_MERGED', 'S2_CLASS',
      'W_TAP128', 'W_TAP64', 'W_TAP64X2', 'W_V4', 'W_V3', 'W_V3N128', 'W_V3N256', 'W_V2_128', 'W_V2_64'])}
 ROUTE_FWD, ROUTE_DGRAD, ROUTE_WGRAD = 0, 1, 2
+
+# the DMY_IOU_* codes of include/dmayolo.h (append only): the box criterion of dmy_yolo_loss_level_iou /
+# dmy_yolo_loss_level_focal_iou / dmy_bbox_iou_eval, keyed by ComputeLoss's iou_type names
+IOU_KIND = {'siou': 0, 'ciou': 1, 'diou': 2, 'giou': 3, 'iou': 4}
 
 # symbols whose argtypes dmayolo/optim.py sets itself (multi-tensor optimizer / GradScaler / EMA kernels)
 SELF_BOUND = {'dmy_chunk_size', 'dmy_sgd', 'dmy_adam', 'dmy_ema', 'dmy_amp_check', 'dmy_amp_update'}

@@ -11,9 +11,16 @@ kernels through the dmy_yolo_loss_level_focal / dmy_yolo_loss_finalize_balance e
 float64 device tensor owned by the ComputeLoss object and updated by the finalize kernel, so a step never
 reads it back (the reference's .item() per level) and stays graph-capturable.  With fl_gamma == 0 and
 autobalance off the original entries run, unchanged.
+
+ComputeLoss(model, iou_type=...) or hyp['iou_type'] picks the box criterion, the keyword of the reference's bbox_iou
+call at utils/loss.py:185: 'siou' (the reference's own, the default), 'ciou', 'diou', 'giou' or 'iou'
+(utils/metrics.py:192-252).  It is a compile-time parameter of the target kernel, reached through the
+dmy_yolo_loss_level_iou / dmy_yolo_loss_level_focal_iou entries; with 'siou' those run the kernels of the original
+entries.
 """
 import torch
 
+from .._lib import IOU_KIND
 from ..functional import call, ptr, stream, dcode
 from .torch_utils import de_parallel
 
@@ -68,9 +75,9 @@ class _YoloLossFn(torch.autograd.Function):
             tail = (float(bs), ptr(ii[0]), ptr(ii[1]), ptr(ii[2]), ptr(ii[3]), ptr(ii[4]), ptr(tbox), ptr(anch),
                     ptr(cnt), cap, ptr(G), ptr(tobj), ptr(part[PR * i:]), ptr(tgrad), ptr(links), stream())
             if bal is None:
-                call('dmy_yolo_loss_level', *head, float(cl._balance[i]), *tail)
+                call('dmy_yolo_loss_level_iou', *head, float(cl._balance[i]), *tail, cl.iou_kind)
             else:
-                call('dmy_yolo_loss_level_focal', *head, ptr(bal), i, float(cl.fl_gamma), *tail)
+                call('dmy_yolo_loss_level_focal_iou', *head, ptr(bal), i, float(cl.fl_gamma), *tail, cl.iou_kind)
             Gs.append(G)
         loss = torch.empty(1, dtype=torch.float32, device=dev)
         items = torch.empty(3, dtype=torch.float32, device=dev)
@@ -98,14 +105,29 @@ class _YoloLossFn(torch.autograd.Function):
 
 
 class ComputeLoss:
-    """utils/loss.py:135-218 (SIoU, anchor-based), with the focal wrapper (hyp['fl_gamma'] > 0) and autobalance.
+    """utils/loss.py:135-218 (anchor-based), with the focal wrapper (hyp['fl_gamma'] > 0) and autobalance.
+
+    iou_type (default hyp.get('iou_type', 'siou'), case-insensitive) is the box criterion, named after the keyword
+    the reference's `bbox_iou(pbox.T, tbox[i], x1y1x2y2=False, ...)` call at utils/loss.py:185 would carry
+    (utils/metrics.py:192-252):
+      'siou'  SIoU=True   the reference's own call, the default
+      'ciou'  CIoU=True   what upstream YOLOv5 trains with; alpha is a constant, as under the reference's no_grad
+      'diou'  DIoU=True
+      'giou'  GIoU=True
+      'iou'   no keyword  plain intersection over union
+    Any other name raises ValueError here, before anything is launched.
 
     Autobalance deviates from the reference in one place: a level whose objectness loss is exactly 0 (or not
     finite) keeps its balance for that step, where the reference's `0.0001 / obji.item()` raises
     ZeroDivisionError.  Under DDP every rank keeps its own balance, as in the reference."""
 
-    def __init__(self, model, autobalance=False):
+    def __init__(self, model, autobalance=False, iou_type=None):
         h = model.hyp
+        self.iou_type = str(h.get('iou_type', 'siou') if iou_type is None else iou_type).lower()
+        if self.iou_type not in IOU_KIND:
+            raise ValueError(f'iou_type {iou_type if iou_type is not None else h.get("iou_type")!r}: '
+                             f'expected one of {sorted(IOU_KIND)}')
+        self.iou_kind = IOU_KIND[self.iou_type]
         self.fl_gamma = float(h.get('fl_gamma', 0.0))
         assert 0.0 <= self.fl_gamma < float('inf'), f'fl_gamma {self.fl_gamma} must be finite and >= 0'
         self.cp, self.cn = smooth_BCE(eps=h.get('label_smoothing', 0.0))

@@ -4,6 +4,7 @@ and the per-class AP integration on the host, as the reference does it.
   process_batch        val.py:62-83 (+ box_iou utils/metrics.py:254-276)  -> dmy_process_batch (HIP)
   process_batch_multi  the same for a whole batch of images in one launch
   ConfusionMatrix      utils/metrics.py:114-189 (its own class-agnostic matching)  -> dmy_confusion_matrix (HIP)
+  bbox_iou             utils/metrics.py:192-252 (IoU / GIoU / DIoU / CIoU / SIoU, grad of box1)  -> dmy_bbox_iou_eval (HIP)
   ap_per_class         utils/metrics.py:21-87   (numpy on the host, like the reference: a few thousand
   compute_ap           utils/metrics.py:90-116   scalars per validation run, not a device workload)
   fitness              utils/metrics.py:15-18
@@ -14,7 +15,7 @@ from pathlib import Path
 import numpy as np
 import torch
 
-from .._lib import call, ptr, stream
+from .._lib import IOU_KIND, call, ptr, stream
 
 _trapz = getattr(np, 'trapezoid', None) or np.trapz  # numpy 2 renamed trapz (same rule)
 
@@ -139,6 +140,62 @@ class ConfusionMatrix:
         """utils/metrics.py:187-189: one line per row, the values separated by blanks"""
         for row in self.matrix:
             print(' '.join(str(v) for v in row))
+
+
+def iou_kind(GIoU=False, DIoU=False, CIoU=False, SIoU=False):
+    """bbox_iou's keywords -> the DMY_IOU_* code, with the precedence of utils/metrics.py:216-252: SIoU first, then
+    DIoU before CIoU (metrics.py:241-243), GIoU only when none of those three is set, else the plain IoU"""
+    name = 'siou' if SIoU else 'diou' if DIoU else 'ciou' if CIoU else 'giou' if GIoU else 'iou'
+    return IOU_KIND[name]
+
+
+class _BboxIouFn(torch.autograd.Function):
+    """value and d iou / d box1 from one dmy_bbox_iou_eval launch (forward-mode duals); backward scales the kept
+    gradient by the upstream one"""
+
+    @staticmethod
+    def forward(ctx, box1, box2, kind, xyxy):
+        n = box2.shape[0]
+        ctx.b1_shape = tuple(box1.shape)
+        b1 = box1.detach().float()
+        b1 = (b1[None].expand(n, 4) if b1.dim() == 1 else b1.t()).contiguous()  # [n, 4] rows, a [4] box broadcast
+        b2 = box2.detach().float().contiguous()
+        iou = torch.empty(n, dtype=torch.float32, device=b2.device)
+        g = torch.empty((n, 4), dtype=torch.float32, device=b2.device)
+        call('dmy_bbox_iou_eval', kind, int(bool(xyxy)), ptr(b1), ptr(b2), ptr(iou), ptr(g), n, stream())
+        ctx.save_for_backward(g)
+        ctx.b1_dtype = box1.dtype
+        return iou
+
+    @staticmethod
+    def backward(ctx, diou):
+        g, = ctx.saved_tensors
+        gb = g * diou.float()[:, None]  # [n, 4]
+        gb = gb.sum(0) if len(ctx.b1_shape) == 1 else gb.t()
+        return gb.to(ctx.b1_dtype), None, None, None
+
+
+def bbox_iou(box1, box2, x1y1x2y2=True, GIoU=False, DIoU=False, CIoU=False, SIoU=False, eps=1e-7):
+    """utils/metrics.py:192-252 on the GPU, through the loss kernel's own device functions (csrc/iou.h):
+    box1 is [4] or [4, n], box2 is [n, 4]; the return is [n] fp32.  A [4] box1 is taken against every row of box2.
+    x1y1x2y2=True takes the corners as given, False takes (x, y, w, h).  The keywords have the reference's precedence
+    (iou_kind above).  Differentiable with respect to box1 (a broadcast [4] box gets the sum over n); the gradient is
+    the forward-mode dual of the same evaluation, with the reference's tie rules and CIoU's constant alpha.
+
+    NotImplementedError: box2 requiring grad (box 2 is a constant in the kernel), an eps other than 1e-7 (compiled
+    in), CPU tensors (there is no CPU path)."""
+    if box1.device.type != 'cuda' or box2.device.type != 'cuda':
+        raise NotImplementedError('bbox_iou runs on the gfx950 kernel: tensors must be on a GPU')
+    if eps != 1e-7:
+        raise NotImplementedError(f'bbox_iou: eps is compiled in as 1e-7, got {eps}')
+    if box2.requires_grad and torch.is_grad_enabled():
+        raise NotImplementedError('bbox_iou: box2 is a constant of the kernel, it cannot require grad')
+    if box2.dim() != 2 or box2.shape[1] != 4:
+        raise ValueError(f'bbox_iou: box2 must be [n, 4], got {tuple(box2.shape)}')
+    n = box2.shape[0]
+    if box1.shape[0] != 4 or box1.dim() > 2 or (box1.dim() == 2 and box1.shape[1] != n):
+        raise ValueError(f'bbox_iou: box1 must be [4] or [4, {n}], got {tuple(box1.shape)}')
+    return _BboxIouFn.apply(box1, box2, iou_kind(GIoU, DIoU, CIoU, SIoU), x1y1x2y2)
 
 
 def compute_ap(recall, precision):

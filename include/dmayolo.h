@@ -479,6 +479,37 @@ int dmy_loss_grad(int dtype, const float* grad, const float* upstream, void* dp,
 /* SIoU (utils/metrics.py:192-235, bbox_iou(..., x1y1x2y2=False, SIoU=True)) of n xywh pairs through the
  * loss kernel's device function: iou [n] and d iou / d b1 [n][4] (forward-mode duals). */
 int dmy_siou_eval(const float* b1, const float* b2, float* iou, float* grad_b1, int n, void* stream);
+/* The box criterion of the loss: the keyword of the reference's bbox_iou call at utils/loss.py:185
+ * (utils/metrics.py:192-252).  Append only, never renumber. */
+#define DMY_IOU_SIOU 0  /* SIoU=True, metrics.py:219-235: what the reference's ComputeLoss passes */
+#define DMY_IOU_CIOU 1  /* CIoU=True, metrics.py:238-247: alpha = v / (v - iou + (1 + eps)) is a constant (no_grad) */
+#define DMY_IOU_DIOU 2  /* DIoU=True, metrics.py:238-242: iou - rho2 / c2 */
+#define DMY_IOU_GIOU 3  /* GIoU=True, metrics.py:248-250: iou - (c_area - union) / c_area */
+#define DMY_IOU_PLAIN 4 /* no keyword, metrics.py:215, 252: inter / union */
+/* dmy_yolo_loss_level / dmy_yolo_loss_level_focal (utils/loss.py:167-218) with the box term's criterion chosen by
+ * iou_kind, the last argument; every other argument, buffer and workspace as there.  DMY_IOU_SIOU runs the very
+ * kernels of those entries; the other kinds are further instances of the same target kernel, so tobj =
+ * max(clamp(iou, 0)), the per-cell ordered gradient sums and the block partials are unchanged (no float atomics, no
+ * host read).  An unknown iou_kind returns hipErrorInvalidValue and launches nothing. */
+int dmy_yolo_loss_level_iou(int dtype, const void* p, long sb, long sa, long sh, long sw, int N, int na, int H, int W,
+                            int no, int nc, float box_gain, float obj_gain, float cls_gain, float cls_pw, float obj_pw,
+                            float cp, float cn, float balance, float bs, const int* b, const int* a, const int* gj,
+                            const int* gi, const int* tcls, const float* tbox, const float* anch, const int* count,
+                            int cap, float* grad, float* tobj, float* part, float* tgrad, int* links, void* stream,
+                            int iou_kind);
+int dmy_yolo_loss_level_focal_iou(int dtype, const void* p, long sb, long sa, long sh, long sw, int N, int na, int H,
+                                  int W, int no, int nc, float box_gain, float obj_gain, float cls_gain, float cls_pw,
+                                  float obj_pw, float cp, float cn, const double* balance, int level, float fl_gamma,
+                                  float bs, const int* b, const int* a, const int* gj, const int* gi, const int* tcls,
+                                  const float* tbox, const float* anch, const int* count, int cap, float* grad,
+                                  float* tobj, float* part, float* tgrad, int* links, void* stream, int iou_kind);
+/* bbox_iou (utils/metrics.py:192-252, eps = 1e-7) of n box pairs through the loss kernel's device functions:
+ * iou [n] and d iou / d b1 [n][4] by forward-mode duals, box 2 constant.  xyxy = 0: both boxes are (x, y, w, h)
+ * (x1y1x2y2=False, metrics.py:200-204) and the gradient is with respect to those; xyxy != 0: (x1, y1, x2, y2) used as
+ * given (metrics.py:197-199), gradient with respect to the corners.  torch.min / torch.max ties split the gradient,
+ * clamp(0) passes it at 0.  n <= 0 launches nothing; an unknown iou_kind returns hipErrorInvalidValue. */
+int dmy_bbox_iou_eval(int iou_kind, int xyxy, const float* b1, const float* b2, float* iou, float* grad_b1, int n,
+                      void* stream);
 
 /* ---- non_max_suppression (utils/general.py:633-725 -> torchvision.ops.nms at :708) */
 int dmy_nms_candidates(const float* pred, int nimg, int A, int no, float conf, int multi_label,
