@@ -187,6 +187,10 @@ SIGNATURES = {
     'dmy_nms_greedy': [P, I, I, I, F, I, I, I, P, L, P, P, P, P, P, P],
     'dmy_nms_mask_rows': [],
     'dmy_nms_greedy_mask': [P, I, I, I, F, I, I, I, P, L, P, P, P, P, P, P, P],
+    'dmy_nms_candidates_labels': [P, P, P, I, I, I, F, I, P, P, L, P, P],
+    'dmy_nms_greedy_kind': [I, P, P, P, I, I, I, F, I, I, I, P, L, P, P, P, P, P, P],
+    'dmy_nms_greedy_mask_kind': [I, P, P, P, I, I, I, F, I, I, I, P, L, P, P, P, P, P, P],
+    'dmy_nms_merge': [P, P, P, I, I, I, F, I, I, I, P, L, P, P, P, P, P, P, P, P],
     # wbf.hip
     'dmy_wbf_max_rows': [],
     'dmy_wbf_workspace_bytes': [I, I],

@@ -79,17 +79,18 @@ class GraphedDetector:
 
     @torch.no_grad()
     def detect(self, x, conf_thres=0.25, iou_thres=0.45, classes=None, agnostic=False, multi_label=False,
-               max_det=300, augment=False):
-        """eval forward + non_max_suppression (utils/general.py:633-725 arguments, merge=False) as one graph replay:
-        returns (list of (k, 6) detections per image, (z, per-level outputs)).  The detections are views of the
-        graph's static output buffer, valid until the next call (as the forward's outputs are).  augment: the
-        test-time-augmented forward (detect.py --augment) in the same single graph; the second output is then
-        (z, None)."""
+               max_det=300, augment=False, merge=False, redundant=True, nms_type='iou'):
+        """eval forward + non_max_suppression (utils/general.py:633-761 arguments; merge, redundant and nms_type as
+        utils.general.non_max_suppression takes them) as one graph replay: returns (list of (k, 6) detections per
+        image, (z, per-level outputs)).  The detections are views of the graph's static output buffer, valid until
+        the next call (as the forward's outputs are).  augment: the test-time-augmented forward (detect.py --augment)
+        in the same single graph; the second output is then (z, None).  A changed NMS mode re-records.  `labels`, a
+        validation-only input, is not offered here."""
         from .utils.general import nms_finish, non_max_suppression, _CAP_HINT
         if self.model.training:
             self.model.eval()
         args = dict(conf_thres=conf_thres, iou_thres=iou_thres, classes=classes, agnostic=agnostic,
-                    multi_label=multi_label, max_det=max_det)
+                    multi_label=multi_label, max_det=max_det, merge=merge, redundant=redundant, nms_type=nms_type)
         key = tuple(sorted((k, str(v)) for k, v in args.items()))
         cur = getattr(self, 'dkey', None)
         if (cur is None or self._state_key(x) != cur[0] or cur[1] != key or cur[3] != bool(augment) or

@@ -17,6 +17,8 @@ statistics are taken from the fused rows.
 Confusion matrix (val.py:178, 263-264): run(..., confusion_matrix=utils.metrics.ConfusionMatrix(nc)) feeds the instance
 every batch's native-space (predn, labelsn) pairs in one launch, for the images that have both labels and predictions;
 the caller reads .matrix / calls .plot() afterwards.  Without an instance nothing of it runs.
+save_hybrid (val.py:228-231): run(..., save_hybrid=True) hands the pixel-scaled labels of the batch to
+non_max_suppression(labels=...), which appends them to every image's candidates.
 Out of scope (control plane): plots, COCO-JSON, txt saving.
 """
 import numpy as np
@@ -112,7 +114,7 @@ def fused_detections(outs, img_hw, conf_thres, iou_thres, max_det, single_cls, w
 
 @torch.no_grad()
 def run(model, batches, nc, conf_thres=0.001, iou_thres=0.6, max_det=300, single_cls=False, compute_loss=None,
-        augment=False, wbf=None, confusion_matrix=None):
+        augment=False, wbf=None, confusion_matrix=None, save_hybrid=False):
     """Returns ((mp, mr, map50, map, *loss), maps [nc], seen, nt [nc]) like val.py:303-311.  augment: the model's
     test-time-augmented forward (val.py:213); it has no per-level outputs, so it excludes compute_loss.
     model may be a list or tuple of models with wbf=dict(iou_thr=0.67, skip_box_thr=0.01, weights=None) (missing
@@ -120,7 +122,11 @@ def run(model, batches, nc, conf_thres=0.001, iou_thres=0.6, max_det=300, single
     boxes fusion over the network-size image makes the rows the statistics see.  The fused path has no per-level
     outputs either, so it excludes compute_loss.
     confusion_matrix: an optional utils.metrics.ConfusionMatrix, updated in place from every batch (val.py:263-264);
-    the return value does not change."""
+    the return value does not change.
+    save_hybrid: the batch's pixel-scaled labels join every image's NMS candidates as apriori rows (val.py:228-231,
+    utils.general.non_max_suppression's labels=); the ensemble path has one NMS per model, so it excludes wbf."""
+    if save_hybrid and wbf is not None:
+        raise ValueError('save_hybrid=True adds the labels to one NMS call: wbf runs one per model (val.py:228-231)')
     if augment and compute_loss:
         raise ValueError('augment=True returns no per-level outputs for compute_loss (val.py:213-217)')
     many = isinstance(model, (list, tuple))
@@ -162,7 +168,8 @@ def run(model, batches, nc, conf_thres=0.001, iou_thres=0.6, max_det=300, single
         if wbf is not None:
             out = fused_detections(outs, (height, width), conf_thres, iou_thres, max_det, single_cls, wbf)
         else:
-            out = non_max_suppression(out, conf_thres, iou_thres, multi_label=True, agnostic=single_cls,
+            apriori = [targets[targets[:, 0] == si, 1:] for si in range(nb)] if save_hybrid else ()  # pixel (cls, xywh)
+            out = non_max_suppression(out, conf_thres, iou_thres, labels=apriori, multi_label=True, agnostic=single_cls,
                                       max_det=max_det)
         nbatches += 1
         seen += len(out)

@@ -526,6 +526,37 @@ int dmy_nms_mask_rows(void);
 int dmy_nms_greedy_mask(const float* pred, int nimg, int A, int no, float iou, int agnostic, int max_det, int max_nms,
                         const unsigned long long* keys, long cap, int* counts, float* boxes,
                         unsigned long long* mask, float* out, int* nkeep, int* ncand, void* stream);
+/* ---- the modes of non_max_suppression beyond its default call; the entries above run that one, unchanged.
+ * Apriori label rows (utils/general.py:663-670, the autolabel / --save-hybrid input of val.py:228-231): labels
+ * [sum n_i, 5] = (cls, x, y, w, h) in pixels, packed image after image, label_off [nimg + 1] their offsets.  Label k of
+ * an image is row A + k of that image in every key: box = the label's xywh, obj = 1, one-hot class (score 1.0 * 1.0),
+ * after the prediction rows in the index order.  A label whose class is outside [0, nc) is dropped.  The later
+ * entries of a call read such rows from the same table (nullable there, both pointers or neither). */
+int dmy_nms_candidates_labels(const float* pred, const float* labels, const int* label_off, int nimg, int A, int no,
+                              float conf, int multi_label, const unsigned char* class_ok, unsigned long long* keys,
+                              long cap, int* counts, void* stream);
+/* Criterion NMS (NMS() of utils/general.py:727-761 over bbox_iou, utils/general.py:764-824): dmy_nms_greedy /
+ * dmy_nms_greedy_mask with the suppression test chosen by iou_kind, a DMY_IOU_* code.  DMY_IOU_PLAIN is the default
+ * path's torchvision test (IoU > thr); DMY_IOU_GIOU / _DIOU / _CIOU evaluate bbox_iou(box1 = the kept, earlier
+ * candidate, box2 = the later one, x1y1x2y2=True, ...) in fp32 with one rounding per operation and suppress iff
+ * !(value <= thr), so a NaN suppresses.  DMY_IOU_SIOU (which NMS() never reaches) and unknown codes return
+ * hipErrorInvalidValue.  The mask form takes no boxes scratch. */
+int dmy_nms_greedy_kind(int iou_kind, const float* pred, const float* labels, const int* label_off, int nimg, int A,
+                        int no, float iou, int agnostic, int max_det, int max_nms, const unsigned long long* keys,
+                        long cap, int* counts, float* boxes, float* out, int* nkeep, int* ncand, void* stream);
+int dmy_nms_greedy_mask_kind(int iou_kind, const float* pred, const float* labels, const int* label_off, int nimg,
+                             int A, int no, float iou, int agnostic, int max_det, int max_nms,
+                             const unsigned long long* keys, long cap, int* counts, unsigned long long* mask,
+                             float* out, int* nkeep, int* ncand, void* stream);
+/* Merge-NMS (utils/general.py:712-718), after a greedy launch that was given ncand = NULL (counts still holds the
+ * candidate counts) and wrote its keep counts to nk, a device vector.  For an image with 1 < n < 3000 candidates every
+ * kept row becomes sum_j w[j] xyxy[j] / sum_j w[j] over all n candidates, w[j] = (box_iou(offset box i, offset box j)
+ * > iou) * score[j] (utils/metrics.py:254-276), the sums in fp64, one division and rounding to fp32; with redundant,
+ * rows with no more than one hit are dropped and the rest move up.  Other images keep their rows.  merged [nimg,
+ * max_det, 6] and hits [nimg, max_det] are scratch.  nkeep gets the final keep counts; ncand as in dmy_nms_greedy. */
+int dmy_nms_merge(const float* pred, const float* labels, const int* label_off, int nimg, int A, int no, float iou,
+                  int agnostic, int max_det, int redundant, const unsigned long long* keys, long cap, int* counts,
+                  const int* nk, float* merged, int* hits, float* out, int* nkeep, int* ncand, void* stream);
 
 /* ---- Swin / C3STR (models/common.py:452-654): LayerNorm, shifted-window attention core with the
  *      reference's mask semantics, per-sample DropPath scale (common.py:386-403) */
