@@ -21,7 +21,7 @@ P, I, L, F, D = ctypes.c_void_p, ctypes.c_int, ctypes.c_long, ctypes.c_float, ct
 # *_last_rows queries, else int (a hipError_t, a size for the *_rows / *_blocks / *_groups queries, or a KERN code
 # for dmy_conv_route)
 SIGNATURES = {
-    # conv.hip (forward, data-grad, the route query of all three passes)
+    # conv.hip (forward, data-grad, the route query of all three passes, the fp8 forward and its quantisation)
     'dmy_conv_fwd_partial_rows': [L, I],
     'dmy_conv_fwd_bound_rows': [L, I],
     'dmy_conv_fwd_last_rows': [],
@@ -32,16 +32,21 @@ SIGNATURES = {
     'dmy_conv_fwd_splitk_elems': [I, P, P, P, I, I, I, I, L, I, I, I, I, I, I, I, L],
     'dmy_conv_fwd_act_ws': [I, P, P, P, P, I, I, I, I, L, I, I, I, I, I, I, I, L, P, P, I, P, L, P, L, P],
     'dmy_conv_route': [I, I, P, P, P, I, I, I, I, L, I, I, I, I, I, I, I, L, I],
-    # conv_wgrad.hip (weight-grad, weight prep; dmy_image_s2d, the image side of the s2d stem, is eltwise.hip's)
+    'dmy_fp8_quant_ws_elems': [],
+    'dmy_fp8_quant': [P, L, I, L, P, P, P],
+    'dmy_conv_fwd_fp8_partial_rows': [L, I],
+    'dmy_conv_fwd_fp8': [P, P, P, P, P, P, P, P, I, I, I, I, I, I, I, I, I, I, I, L, P, P, I, P, L, P],
+    # conv_wgrad.hip (weight-grad, weight prep)
     'dmy_conv_wgrad': [I, P, P, P, I, I, I, I, L, I, I, I, I, I, I, I, L, P],
     'dmy_conv_wprep_multi': [I, P, I, P],
     'dmy_conv_wprep_s2d': [I, P, P, I, I, I, P],
     'dmy_conv_wgrad_s2d_to_oihw': [P, P, I, I, I, P],
-    'dmy_image_s2d': [I, I, P, P, I, I, I, I, I, F, P],
     'dmy_conv_wgrad_ex': [I, P, P, P, I, I, I, I, L, I, I, I, I, I, I, I, L, I, P],
     'dmy_conv_wgrad_ws_elems': [I, P, P, I, I, I, I, L, I, I, I, I, I, I, I, L, I],
     'dmy_conv_wgrad_det': [I, P, P, P, I, I, I, I, L, I, I, I, I, I, I, I, L, I, P, L, P],
     'dmy_conv_wprep': [I, P, P, P, I, I, I, I, I, P],
+    'dmy_conv_wprep_fp8': [P, P, P, I, I, I, I, P],
+    'dmy_conv_wgrad_to_oihw': [P, P, I, I, I, I, I, P],
     # dwconv.hip
     'dmy_dwconv_ok': [I, P, P, P, I, I, I, I, I, I, L, I, I, I, I, I, I, L],
     'dmy_dwconv_fwd_rows': [L, I],
@@ -78,12 +83,6 @@ SIGNATURES = {
     'dmy_letterbox_desc_bytes': [],
     'dmy_letterbox_batch': [I, P, P, I, P, I, I, I, I, F, P],
     'dmy_scale_boxes': [P, P, P, P, P, P, I, I, P],
-    'dmy_fp8_quant_ws_elems': [],
-    'dmy_fp8_quant': [P, L, I, L, P, P, P],
-    'dmy_conv_wprep_fp8': [P, P, P, I, I, I, I, P],
-    'dmy_conv_fwd_fp8_partial_rows': [L, I],
-    'dmy_conv_fwd_fp8': [P, P, P, P, P, P, P, P, I, I, I, I, I, I, I, I, I, I, I, L, P, P, I, P, L, P],
-    'dmy_conv_wgrad_to_oihw': [P, P, I, I, I, I, I, P],
     # bn.hip
     'dmy_bn_partial_rows': [L],
     'dmy_bn_stats': [I, P, L, L, I, P, P, P],
@@ -99,6 +98,9 @@ SIGNATURES = {
     'dmy_bn_reduce_rows': [I, P, L, P, L, L, I],
     'dmy_colsum2_rows': [L],
     'dmy_colsum2': [P, P, L, I, P, P, P],
+    'dmy_scgate_bn_rows': [I, I, I, I],
+    'dmy_scgate_bn_fwd': [P, L, P, P, P, P, P, I, I, I, I, I, I, P],
+    'dmy_scgate_bn_bwd': [P, L, P, P, P, P, P, P, P, P, P, I, I, I, I, I, I, P, P, P],
     # spd.hip
     'dmy_bn_act_s2d_fwd': [I, P, L, P, P, I, P, L, I, I, I, I, P],
     'dmy_bn_bwd_reduce_s2d_rows': [I, L, I],
@@ -115,6 +117,7 @@ SIGNATURES = {
     'dmy_layerscale_bwd_rows': [L],
     'dmy_layerscale_bwd': [I, P, L, P, P, P, L, I, P, P],
     # eltwise.hip
+    'dmy_image_s2d': [I, I, P, P, I, I, I, I, I, F, P],
     'dmy_maxpool_fwd': [I, P, L, P, L, P, I, I, I, I, I, P],
     'dmy_maxpool_chain3_fwd': [I, P, L, P, P, P, L, I, I, I, I, I, P],
     'dmy_maxpool_bwd': [I, P, L, P, P, L, I, I, I, I, I, I, P],
@@ -129,9 +132,6 @@ SIGNATURES = {
     'dmy_bifpn_wgrad': [P, I, I, P, F, P, P],
     'dmy_scgate_fwd': [I, P, L, P, P, P, I, I, I, I, I, I, P],
     'dmy_scgate_bwd': [I, P, L, P, P, P, P, P, L, I, I, I, I, I, I, I, P],
-    'dmy_scgate_bn_rows': [I, I, I, I],
-    'dmy_scgate_bn_fwd': [P, L, P, P, P, P, P, I, I, I, I, I, I, P],
-    'dmy_scgate_bn_bwd': [P, L, P, P, P, P, P, P, P, P, P, I, I, I, I, I, I, P, P, P],
     'dmy_ca_pool_fwd': [I, P, L, P, I, I, I, I, P],
     'dmy_ca_pool_bwd': [I, P, P, L, I, I, I, I, I, P],
     'dmy_ca_apply_fwd': [I, P, L, P, P, P, L, I, I, I, I, P],
@@ -140,6 +140,15 @@ SIGNATURES = {
     'dmy_nhwc_to_nchw_f32': [I, P, L, P, I, I, I, I, P],
     'dmy_pointwise': [I, I, I, P, P, P, L, F, P],
     'dmy_cast': [I, I, P, P, L, F, P],
+    'dmy_space_to_depth': [I, P, L, P, L, I, I, I, I, I, P],
+    'dmy_gpool_ws_bytes': [I, I, I, I],
+    'dmy_gpool_fwd': [I, P, L, I, I, I, P, P, P, P],
+    'dmy_gpool_bwd': [I, P, P, P, L, I, I, I, I, P],
+    'dmy_halves_sigmoid': [I, P, I, I, P, P, P, P],
+    'dmy_cbam_in_fwd': [I, P, L, P, I, I, I, P, P, P, P],
+    'dmy_cbam_in_bwd_ws_elems': [I, I, I],
+    'dmy_cbam_in_bwd': [I, P, L, P, P, L, P, P, I, I, I, P, L, I, P, P, P],
+    'dmy_pixscale': [I, P, P, L, I, I, I, P, L, P, L, P, P, P],
     # tta.hip
     'dmy_tta_image': [I, I, P, P, I, I, I, I, I, I, F, I, I, I, I, I, F, P],
     # detect_loss.hip
@@ -166,15 +175,6 @@ SIGNATURES = {
     'dmy_tal_loss': [I, P, L, L, L, P, L, L, L, I, I, I, P, P, P, P, I, F, F, F, P, P, P, P, P],
     'dmy_tal_flatten': [I, P, L, I, I, I, I, I, I, P, I, P],
     'dmy_tal_detect_out': [I, P, I, I, I, P, P, P, P, P],
-    'dmy_space_to_depth': [I, P, L, P, L, I, I, I, I, I, P],
-    'dmy_gpool_ws_bytes': [I, I, I, I],
-    'dmy_gpool_fwd': [I, P, L, I, I, I, P, P, P, P],
-    'dmy_gpool_bwd': [I, P, P, P, L, I, I, I, I, P],
-    'dmy_halves_sigmoid': [I, P, I, I, P, P, P, P],
-    'dmy_cbam_in_fwd': [I, P, L, P, I, I, I, P, P, P, P],
-    'dmy_cbam_in_bwd_ws_elems': [I, I, I],
-    'dmy_cbam_in_bwd': [I, P, L, P, P, L, P, P, I, I, I, P, L, I, P, P, P],
-    'dmy_pixscale': [I, P, P, L, I, I, I, P, L, P, L, P, P, P],
     # mha.hip
     'dmy_mha_fwd': [I, P, L, P, L, P, L, P, L, P, I, I, I, I, F, P],
     'dmy_mha_fwd_ref': [I, P, L, P, L, P, L, P, L, P, I, I, I, I, F, P],
@@ -250,7 +250,14 @@ def _load():
 lib = _load()
 
 
+# the launch observer: None, or a callable given (symbol name, argument tuple) ahead of every call() below, whichever
+# module imported `call` (the launch-counting tests, tools/gpu/hor_micro.py).  It only observes: its result is ignored
+TRACE = [None]
+
+
 def call(name, *args):
+    if TRACE[0] is not None:
+        TRACE[0](name, args)
     rc = getattr(lib, name)(*args)
     if name.endswith(('_rows', '_blocks', '_groups', '_bytes', '_elems', '_ok', '_route')):
         return rc

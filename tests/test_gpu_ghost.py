@@ -192,23 +192,22 @@ def test_ghost_model_one_launch_eval_fuse_and_graph(dtype):
     """eval: one launch per conv (no separate BN pass, depthwise layers on dmy_dwconv_fwd_act); fuse() changes the
     decoded output by no more than test_inference_epilogue_matches_unfused_and_tracks_updates allows for a fused
     model; GraphedDetector replays the eager forward bit for bit; augment=True runs"""
-    import dmayolo.functional as Fn
+    from dmayolo import _lib
     from dmayolo.infer import GraphedDetector
     fx = Fixture('ghost_v5s')
     m = _model(fx, dtype).eval()
     x = fx.t('in.0').cuda()
-    counts, orig = {}, Fn.call
+    counts = {}
 
-    def counting(name, *a):
+    def counting(name, args):  # _lib.call's observer: every launch, from whichever module
         counts[name] = counts.get(name, 0) + 1
-        return orig(name, *a)
     with torch.no_grad():
         ref, _ = m(x)
-        Fn.call = counting
+        _lib.TRACE[0] = counting
         try:
             z, _ = m(x)
         finally:
-            Fn.call = orig
+            _lib.TRACE[0] = None
         assert counts.get('dmy_bn_act_fwd', 0) == 0 and counts.get('dmy_dwconv_fwd', 0) == 0, counts
         assert counts.get('dmy_dwconv_fwd_act', 0) == 32, counts
         assert torch.equal(z, ref)

@@ -361,7 +361,7 @@ def test_no_grad_eval_takes_fused_path_with_trainable_params():
     """a no-grad eval forward must use the one-launch conv + eval-BN + act kernels even when the parameters
     require grad (detect.py / val on a freshly loaded model): ctx.needs_input_grad mirrors requires_grad under
     torch.no_grad(), so it alone would send every layer down the training path (weight prep, separate BN)"""
-    import dmayolo.functional as Fn
+    from dmayolo import _lib
     from dmayolo.models.yolo import Model
     from dmayolo.synthetic import images
     torch.manual_seed(0)
@@ -369,18 +369,41 @@ def test_no_grad_eval_takes_fused_path_with_trainable_params():
     assert all(p.requires_grad for p in m.parameters())
     x = images(1, 320, device='cuda')
     counts = {}
-    orig = Fn.call
 
-    def counting(name, *a):
+    def counting(name, args):  # _lib.call's observer: every launch, from whichever module
         counts[name] = counts.get(name, 0) + 1
-        return orig(name, *a)
     with torch.no_grad():
         ref, _ = m(x)  # fills the per-layer caches
-        Fn.call = counting
+        _lib.TRACE[0] = counting
         try:
             z, _ = m(x)
         finally:
-            Fn.call = orig
+            _lib.TRACE[0] = None
     assert counts.get('dmy_bn_act_fwd', 0) == 0 and counts.get('dmy_conv_wprep', 0) == 0, counts
     assert counts.get('dmy_conv_fwd_act', 0) > 0
     torch.testing.assert_close(z, ref, rtol=0, atol=0)
+
+
+def test_launch_observer_reaches_every_module():
+    """_lib.TRACE sees the launches of every module that imported `call`, not only dmayolo.functional's: one no-grad
+    eval forward records the conv engine's one-launch forward and the Detect decode issued from models/yolo.py"""
+    from dmayolo import _lib
+    from dmayolo.models.yolo import Model
+    from dmayolo.synthetic import images
+    torch.manual_seed(0)
+    m = Model(os.path.join(CFG, 'yolov5n.yaml'), nc=4).cuda().eval()
+    x = images(1, 64, device='cuda')
+    names = []
+    _lib.TRACE[0] = lambda name, args: names.append(name)
+    try:
+        with torch.no_grad():
+            z, _ = m(x)
+    finally:
+        _lib.TRACE[0] = None
+    assert 'dmy_conv_fwd_act' in names or 'dmy_conv_fwd_act_ws' in names, sorted(set(names))
+    assert 'dmy_detect_decode_levels' in names, sorted(set(names))  # Detect.decode, models/yolo.py
+    n = len(names)
+    with torch.no_grad():
+        m(x)
+    assert len(names) == n  # hook removed: nothing more is recorded
+    assert bool(torch.isfinite(z).all())

@@ -1,5 +1,5 @@
 """Which 1x1 Conv-BN-act backwards of a model take the fused kernel (bwd1x1.hip) and why the others do not: one train
-step at a small resolution with functional._bwd1x1 wrapped, one line per 1x1 train-BN layer.
+step at a small resolution with functional.conv._bwd1x1 wrapped, one line per 1x1 train-BN layer.
 python tools/gpu/diag_bwd1x1.py [yaml] [img] [bs]"""
 import collections
 import os
@@ -16,7 +16,7 @@ from dmayolo.synthetic import images, targets, HYP_VISDRONE, scaled_hyp, CONFIGS
 yml = sys.argv[1] if len(sys.argv) > 1 else 'yolov5l-ca-sppfcspc-bifpn-scconv.yaml'
 img = int(sys.argv[2]) if len(sys.argv) > 2 else 256
 bs = int(sys.argv[3]) if len(sys.argv) > 3 else 2
-orig = fn._bwd1x1
+orig = fn.conv._bwd1x1
 seen = collections.Counter()
 
 
@@ -34,7 +34,7 @@ def wrapped(ctx, dy, dps, x, wt, z, stats, coef):
     return r
 
 
-fn._bwd1x1 = wrapped
+fn.conv._bwd1x1 = wrapped  # the module ConvBNActFn.backward looks it up in
 torch.manual_seed(0)
 m = Model(os.path.join(CONFIGS, yml), nc=10, act_dtype=torch.bfloat16).cuda().train()
 m.hyp = scaled_hyp(HYP_VISDRONE, 10, img)

@@ -6,9 +6,9 @@ of --reps replays after one warm-up.  Every tensor is larger than the 256 MB Inf
 
 `--what hor`: the gate and layer-scale kernels of csrc/hor.hip the same way, on the slices GnConv(128) hands them (pwa
 of the 256-wide fused_x, dw_list[i] of the 248-wide dw_abc, dense pws outputs), each next to a dense copy that moves the
-same number of bytes.  `--what block`: one HorBlock(128) forward + backward at the same map, bf16, every launch between
-two events, summed per launch family (the 1x1 convs told apart by their channel counts); eager, so launch gaps are in
-the step time but not in the family sums.
+same number of bytes.  `--what block`: one HorBlock(128) forward + backward at the same map, bf16, an event ahead of
+every launch (the launch observer of dmayolo._lib), summed per launch family (the 1x1 convs told apart by their channel
+counts); eager, so the host's launch gaps are in the step time.
 
     python tools/gpu/hor_micro.py [--what dw7 hor block] [--batch 32] [--reps 7]
 """
@@ -136,21 +136,18 @@ def block(N, H, W, c, reps):
     with torch.no_grad():
         m.gamma1.fill_(1.0), m.gamma2.fill_(1.0)
     x = act(N, c, H, W).requires_grad_(True)
-    ev, orig = [], Fn.call
+    ev = []
 
-    def timed_call(name, *args):
+    def mark(name, args):  # _lib.call's observer: one event ahead of every launch, from whichever module
         if name.endswith(('_rows', '_blocks', '_ok', '_elems', '_bytes', '_route', '_groups')):
-            return orig(name, *args)
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        r = orig(name, *args)
-        e1.record()
-        ev.append((family(name, args, c), e0, e1))
-        return r
+            return
+        e = torch.cuda.Event(enable_timing=True)
+        e.record()
+        ev.append((family(name, args, c), e))
     tot = {}
     for it in range(reps + 1):
         ev.clear()
-        Fn.call = Fn._lib.call = timed_call
+        Fn._lib.TRACE[0] = mark
         try:
             t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             t0.record()
@@ -158,11 +155,13 @@ def block(N, H, W, c, reps):
             t1.record()
             torch.cuda.synchronize()
         finally:
-            Fn.call = Fn._lib.call = orig
+            Fn._lib.TRACE[0] = None
         if it:  # the first pass warms up
             tot.setdefault('whole step (eager, with gaps)', []).append(t0.elapsed_time(t1) * 1e3)
             fam = {}
-            for f, e0, e1 in ev:
+            # a launch runs from its own event to the next launch's (the last one: to the step's closing event); torch
+            # work between two launches (the loss sum, autograd's adds) is counted with the launch ahead of it
+            for (f, e0), (_, e1) in zip(ev, ev[1:] + [(None, t1)]):
                 fam[f] = fam.get(f, 0.0) + e0.elapsed_time(e1) * 1e3
             for f, v in fam.items():
                 tot.setdefault(f, []).append(v)
