@@ -469,6 +469,101 @@ __global__ void bn_bwd_finalize_kernel(const float* __restrict__ pdb, const floa
   }
 }
 
+// -------- SyncBatchNorm (torch.nn.SyncBatchNorm.forward / its autograd Function, reached by train.py:272-275): the
+// per-rank sums of one layer travel in a slab [R][2C + 1] of doubles, slot r = (sum a[C], sum b[C], n) of rank r.
+// pack: this rank's P partial rows -> slot `rank`, summed per channel exactly as bn_finalize_kernel sums them (same
+// per-thread order, same LDS tree), every other slot zeroed by the same blocks: an all-reduce(SUM) of the slabs then
+// only ever adds zeros to a slot, which is exact, so every rank ends with the same bits whatever order the collective
+// adds in.  One block per channel; block 0 also owns the slots' counts.
+__global__ void bn_sync_pack_kernel(const float* __restrict__ pa, const float* __restrict__ pb, int P, int C,
+                                    double count, double* __restrict__ slab, int R, int rank) {
+  const int c = blockIdx.x;
+  const long S = 2L * C + 1;
+  __shared__ double sa[256], sb[256];
+  double a = 0.0, b = 0.0;
+  // independent loads in flight: the sums stay sequential per thread (same order)
+#pragma unroll 8
+  for (int p = threadIdx.x; p < P; p += blockDim.x) {
+    a += (double)pa[(long)p * C + c];
+    b += (double)pb[(long)p * C + c];
+  }
+  sa[threadIdx.x] = a;
+  sb[threadIdx.x] = b;
+  __syncthreads();
+  for (int s = blockDim.x / 2; s > 0; s >>= 1) {
+    if ((int)threadIdx.x < s) {
+      sa[threadIdx.x] += sa[threadIdx.x + s];
+      sb[threadIdx.x] += sb[threadIdx.x + s];
+    }
+    __syncthreads();
+  }
+  for (int r = threadIdx.x; r < R; r += blockDim.x) {
+    const bool mine = r == rank;
+    double* slot = slab + r * S;
+    slot[c] = mine ? sa[0] : 0.0;
+    slot[C + c] = mine ? sb[0] : 0.0;
+    if (c == 0) slot[2 * C] = mine ? count : 0.0;
+  }
+}
+
+// finalize over the exchanged slab: the R slots added in rank order in double, the global count read from the slab
+// (no host readback), then bn_finalize_kernel's formulas.  One thread per channel: R is a handful, and rank order is a
+// sequential sum.  R == 1 reproduces bn_finalize_kernel bit for bit.
+__global__ void bn_sync_finalize_kernel(const double* __restrict__ slab, int R, int C, const float* __restrict__ gamma,
+                                        const float* __restrict__ beta, float* __restrict__ rmean,
+                                        float* __restrict__ rvar, long long* nbt, float momentum, float eps, int update,
+                                        float* __restrict__ mean, float* __restrict__ invstd, float* __restrict__ scale,
+                                        float* __restrict__ shift) {
+  const int c = blockIdx.x * blockDim.x + threadIdx.x;
+  if (c >= C) return;
+  const long S = 2L * C + 1;
+  double a = slab[c], b = slab[C + c], count = slab[2 * C];
+  for (int r = 1; r < R; ++r) {
+    a += slab[r * S + c];
+    b += slab[r * S + C + c];
+    count += slab[r * S + 2 * C];
+  }
+  const double mu = a / count;
+  double var = b / count - mu * mu;
+  if (var < 0) var = 0;
+  const float is = (float)(1.0 / sqrt(var + (double)eps));
+  mean[c] = (float)mu;
+  invstd[c] = is;
+  const float g = gamma ? gamma[c] : 1.f, bb = beta ? beta[c] : 0.f;
+  scale[c] = g * is;
+  shift[c] = bb - (float)mu * g * is;
+  if (update) {
+    const double unb = count > 1 ? var * count / (count - 1) : var;
+    rmean[c] = (1.f - momentum) * rmean[c] + momentum * (float)mu;
+    rvar[c] = (1.f - momentum) * rvar[c] + momentum * (float)unb;
+    if (c == 0 && nbt) *nbt += 1;
+  }
+}
+
+// backward: dgamma / dbeta from slot `rank` alone (torch's SyncBatchNorm rule: parameter gradients stay local, DDP
+// averages them), ca / cb / cc from all slots in rank order over the global count, bn_bwd_finalize_kernel's formulas
+__global__ void bn_sync_bwd_finalize_kernel(const double* __restrict__ slab, int R, int rank, int C,
+                                            const float* __restrict__ gamma, const float* __restrict__ invstd,
+                                            float* __restrict__ dgamma, float* __restrict__ dbeta,
+                                            float* __restrict__ ca, float* __restrict__ cb, float* __restrict__ cc) {
+  const int c = blockIdx.x * blockDim.x + threadIdx.x;
+  if (c >= C) return;
+  const long S = 2L * C + 1;
+  if (dbeta) dbeta[c] = (float)slab[rank * S + c];
+  if (dgamma) dgamma[c] = (float)slab[rank * S + C + c];
+  double a = slab[c], b = slab[C + c], count = slab[2 * C];
+  for (int r = 1; r < R; ++r) {
+    a += slab[r * S + c];
+    b += slab[r * S + C + c];
+    count += slab[r * S + 2 * C];
+  }
+  const float g = gamma ? gamma[c] : 1.f;
+  const float k = g * invstd[c];
+  ca[c] = k;
+  cb[c] = (float)(-(double)k * a / count);
+  cc[c] = (float)(-(double)k * b / count);
+}
+
 // two-stage column sums of [P][C] float partial pairs -> [S][C]
 __global__ void colsum2_kernel(const float* __restrict__ a, const float* __restrict__ b, long P, int C, int rows_per,
                                float* __restrict__ oa, float* __restrict__ ob) {
@@ -605,6 +700,31 @@ DMY_API int dmy_bn_bwd_finalize(const float* pdb, const float* pdg, int P, int C
                                 const float* invstd, float* dgamma, float* dbeta, float* ca, float* cb, float* cc,
                                 void* stream) {
   return launch(bn_bwd_finalize_kernel, C, stream, pdb, pdg, P, C, count, gamma, invstd, dgamma, dbeta, ca, cb, cc);
+}
+
+static bool sync_ok(const double* slab, int R, int rank, int C) {
+  return slab && !((uintptr_t)slab & 7) && C > 0 && R > 0 && rank >= 0 && rank < R;
+}
+
+DMY_API int dmy_bn_sync_pack(const float* pa, const float* pb, int P, int C, double count, double* slab, int R, int rank,
+                             void* stream) {
+  if (!sync_ok(slab, R, rank, C) || P < 0 || (P > 0 && (!pa || !pb))) return kInvalid;
+  return launch(bn_sync_pack_kernel, C, stream, pa, pb, P, C, count, slab, R, rank);
+}
+
+DMY_API int dmy_bn_sync_finalize(const double* slab, int R, int C, const float* gamma, const float* beta, float* rmean,
+                                 float* rvar, long long* nbt, float momentum, float eps, int update, float* mean,
+                                 float* invstd, float* scale, float* shift, void* stream) {
+  if (!sync_ok(slab, R, 0, C) || (update && (!rmean || !rvar))) return kInvalid;
+  return launch(bn_sync_finalize_kernel, ceil_div(C, 256), stream, slab, R, C, gamma, beta, rmean, rvar, nbt, momentum,
+                eps, update, mean, invstd, scale, shift);
+}
+
+DMY_API int dmy_bn_sync_bwd_finalize(const double* slab, int R, int rank, int C, const float* gamma, const float* invstd,
+                                     float* dgamma, float* dbeta, float* ca, float* cb, float* cc, void* stream) {
+  if (!sync_ok(slab, R, rank, C)) return kInvalid;
+  return launch(bn_sync_bwd_finalize_kernel, ceil_div(C, 256), stream, slab, R, rank, C, gamma, invstd, dgamma, dbeta, ca,
+                cb, cc);
 }
 
 DMY_API int dmy_bn_bwd_apply(int dtype, const void* z, long zps, const void* dy, long dps, const float* scale,

@@ -98,6 +98,9 @@ SIGNATURES = {
     'dmy_bn_reduce_rows': [I, P, L, P, L, L, I],
     'dmy_colsum2_rows': [L],
     'dmy_colsum2': [P, P, L, I, P, P, P],
+    'dmy_bn_sync_pack': [P, P, I, I, D, P, I, I, P],
+    'dmy_bn_sync_finalize': [P, I, I, P, P, P, P, P, F, F, I, P, P, P, P, P],
+    'dmy_bn_sync_bwd_finalize': [P, I, I, I, P, P, P, P, P, P, P, P],
     'dmy_scgate_bn_rows': [I, I, I, I],
     'dmy_scgate_bn_fwd': [P, L, P, P, P, P, P, I, I, I, I, I, I, P],
     'dmy_scgate_bn_bwd': [P, L, P, P, P, P, P, P, P, P, P, I, I, I, I, I, I, P, P, P],

@@ -41,11 +41,11 @@ from .timer import KernelTimer
 from .fp8 import F8_DELAYED, F8_HEADROOM, F8Emit, _F8_WS, _f8_ws, fp8_eligible, _fp8_weight, _fp8_operands, _conv_fp8
 from .spd import MaxPool2Fn, SpdSplitFn, SpaceToDepthFn, _spd_shape
 from .conv import WGRAD_OIHW, WGRAD_ZEROED, DETERMINISTIC, DEFER_AFFINE, BWD1X1, PARAM_GEN, set_deterministic, \
-    ConvGeom, WgradArena, WeightPrep, ConvSpec, BnLink, _SPECS, _PSPECS, spec_for, _param_spec, set_fp8, \
+    ConvGeom, WgradArena, WeightPrep, ConvSpec, BnLink, _SPECS, _PSPECS, spec_for, _param_spec, drop_specs, set_fp8, \
     f8_saturation, prep_weight, eval_coef, ConvBNActFn, conv_bn_act, _wgrad, _launch_conv_fwd, _launch_dw_fwd, \
     _dw_unsupported, _dw_check, _dw_operands, _fold_partials, _conv_operands, _conv_infer, _conv_infer_spd, \
-    _conv_bn_stats, _bn_finalize, _defer_affine, _act_pass, _save_ctx, _pgrad, _wgrad_target, _bn_bwd_coef, _bwd1x1, \
-    _dw_bias_in_wgrad, _act_bias_bwd, _dgrad, _conv_wgrad
+    _conv_bn_stats, _bn_sync, _sync_slab, _bn_finalize, _bn_bwd_finalize, _defer_affine, _act_pass, _save_ctx, \
+    _pgrad, _wgrad_target, _bn_bwd_coef, _bwd1x1, _dw_bias_in_wgrad, _act_bias_bwd, _dgrad, _conv_wgrad
 from .convmix import ConvActBNFn, conv_act_bn, _actbn_stats, _actbn_infer
 from .pool import MaxPoolFn, maxpool_chain3, AvgPoolFn, ResizeFn, ConcatFn, _inplace_concat, AddFn
 from .attention import SCGateFn, CAPoolFn, CAApplyFn, GPoolFn, HalvesSigmoidFn, CBAMInFn, PixScaleFn

@@ -6,6 +6,7 @@ import weakref
 from collections import namedtuple
 
 import torch
+import torch.distributed as dist
 
 from .._lib import call, ptr, stream, ACT_NONE
 from ._base import DT, VW, const_vec, conv_out_hw, dcode, f32, new_act, out_view, pixel_stride, vec_view, \
@@ -140,7 +141,7 @@ class WeightPrep:
 
 
 class ConvSpec:
-    """Static description of one conv(+BN)(+act) layer; `bn` is the live nn.BatchNorm2d (or None).
+    """Static description of one conv(+BN)(+act) layer; `bn` is the live nn.BatchNorm2d / nn.SyncBatchNorm (or None).
     wcache / ecache: inference-only caches of the prepped weight and the eval BN coefficients."""
     __slots__ = ('stride', 'pad', 'act', 'bn', 'wcache', 'ecache', 'fp8', 'f8cache', 'f8_emit', 'defer', 'groups',
                  '__weakref__')
@@ -181,6 +182,19 @@ def _param_spec(w, stride, pad, act, bn):
     if sp is None or sp.bn is not bn:
         sp = ent[1][key] = ConvSpec(stride, pad, act, bn)
     return sp
+
+
+def drop_specs(model):
+    """Forget every cached ConvSpec of `model`'s convs, with the inference caches hanging off them, and bump PARAM_GEN:
+    for a change of module identity behind a conv (its BatchNorm replaced, utils.torch_utils.convert_sync_batchnorm).
+    The next forward builds fresh specs around the live modules."""
+    for m in model.modules():
+        if isinstance(m, torch.nn.Conv2d):
+            _SPECS.pop(m, None)
+            ent = _PSPECS.get(id(m.weight))
+            if ent is not None and ent[0]() is m.weight:
+                ent[1].clear()
+    PARAM_GEN[0] += 1
 
 
 # the two model-level fp8 entry points: they walk the spec registry above, the rest of the fp8 path is fp8.py
@@ -421,7 +435,7 @@ def _conv_infer(x, g, wf, bias, spec, res, rps, out, yps, f8):
     return y
 
 
-def _conv_bn_stats(x, g, wf, bias, z, bn, train_bn, f8):
+def _conv_bn_stats(x, g, wf, bias, z, bn, train_bn, f8, sync=None):
     """The conv launch into z and the BN coefficients -> (scale, shift, mean, invstd).  Train mode: the launch's
     epilogue writes per-row partial sums, folded and finalized (dmy_bn_finalize, which also updates the running
     statistics); eval-mode BN under autograd: scale / shift from the running statistics, mean / invstd unused."""
@@ -442,21 +456,73 @@ def _conv_bn_stats(x, g, wf, bias, z, bn, train_bn, f8):
     if f8 is None and not dw:
         P = call('dmy_conv_fwd_last_rows')
     psum, psq, P = _fold_partials(psum, psq, P, K, dev)
-    _bn_finalize(psum, psq, P, K, M, bn, mean, invstd, scale, shift)
+    _bn_finalize(psum, psq, P, K, M, bn, mean, invstd, scale, shift, sync)
     return scale, shift, mean, invstd
 
 
-def _bn_finalize(psum, psq, P, K, M, bn, mean, invstd, scale, shift):
+def _bn_sync(bn, train_bn):
+    """-> None for a BN layer that normalises with its own rank's statistics, else (process group, world size, rank):
+    the layer exchanges its sums with the other ranks in both directions.  The conditions of
+    torch.nn.SyncBatchNorm.forward: the module type, batch statistics in use, an initialised torch.distributed and a
+    group of more than one rank.  A collective cannot be captured into a graph: such a layer raises under stream
+    capture, and callers ask before the layer's first launch."""
+    if not (train_bn and isinstance(bn, torch.nn.SyncBatchNorm)):
+        return None
+    if not (dist.is_available() and dist.is_initialized()):
+        return None
+    group = bn.process_group
+    world = dist.get_world_size(group)
+    if world <= 1:
+        return None
+    if torch.cuda.is_current_stream_capturing():
+        raise RuntimeError('SyncBatchNorm cannot run under graph capture: its cross-rank exchange of batch statistics '
+                           'is a collective per layer (GraphedTrainStep / torch.cuda.graph); train a converted model '
+                           'eagerly, or leave its BatchNorm2d layers unconverted')
+    return group, world, dist.get_rank(group)
+
+
+def _sync_slab(pa, pb, P, K, M, sync, dev):
+    """The exchange of one synchronised layer, either direction: this rank's P partial rows packed into its slot of the
+    fp64 slab [world][2K + 1] (dmy_bn_sync_pack zeros the other slots), then one all_reduce(SUM) ordered on the current
+    stream -> the slab every rank holds alike.  M: this rank's pixel count (ranks may differ)."""
+    group, world, rank = sync
+    if M < 1:
+        raise RuntimeError('SyncBatchNorm: a rank with no pixels in the batch is not supported')
+    slab = torch.empty(world * (2 * K + 1), dtype=torch.float64, device=dev)
+    call('dmy_bn_sync_pack', ptr(pa), ptr(pb), P, K, float(M), ptr(slab), world, rank, stream())
+    dist.all_reduce(slab, op=dist.ReduceOp.SUM, group=group)
+    return slab
+
+
+def _bn_finalize(psum, psq, P, K, M, bn, mean, invstd, scale, shift, sync=None):
     """dmy_bn_finalize over P rows of per-channel partial sums of M values: writes mean / invstd / scale / shift and,
-    for a training BN that tracks them, updates the running statistics in place"""
+    for a training BN that tracks them, updates the running statistics in place.  sync (_bn_sync): the sums of every
+    rank go into the statistics (dmy_bn_sync_finalize over the exchanged slab), so all ranks write the same bits."""
     upd = int(bn.training and bn.track_running_stats)
     if upd:
         PARAM_GEN[0] += 1  # running stats change behind torch's back: drop inference caches
     mom = bn.momentum if bn.momentum is not None else 0.0
-    call('dmy_bn_finalize', ptr(psum), ptr(psq), P, K, float(M), ptr(bn.weight), ptr(bn.bias),
-         ptr(bn.running_mean) if upd else None, ptr(bn.running_var) if upd else None,
-         ptr(bn.num_batches_tracked) if upd else None, float(mom), float(bn.eps), upd,
-         ptr(mean), ptr(invstd), ptr(scale), ptr(shift), stream())
+    run = (ptr(bn.running_mean) if upd else None, ptr(bn.running_var) if upd else None,
+           ptr(bn.num_batches_tracked) if upd else None, float(mom), float(bn.eps), upd,
+           ptr(mean), ptr(invstd), ptr(scale), ptr(shift), stream())
+    if sync is None:
+        call('dmy_bn_finalize', ptr(psum), ptr(psq), P, K, float(M), ptr(bn.weight), ptr(bn.bias), *run)
+    else:
+        slab = _sync_slab(psum, psq, P, K, M, sync, mean.device)
+        call('dmy_bn_sync_finalize', ptr(slab), sync[1], K, ptr(bn.weight), ptr(bn.bias), *run)
+
+
+def _bn_bwd_finalize(pdb, pdg, P, K, M, gamma, invstd, dgamma, dbeta, ca, cb, cc, sync=None):
+    """dmy_bn_bwd_finalize over P rows of (sum dy, sum dy * xhat) partials of M pixels: dgamma / dbeta and the apply
+    coefficients.  sync (_bn_sync, as the forward decided): ca / cb / cc come from every rank's sums over the global
+    pixel count, dgamma / dbeta stay this rank's own sums (torch's SyncBatchNorm rule: the DDP reducer averages them)."""
+    if sync is None:
+        call('dmy_bn_bwd_finalize', ptr(pdb), ptr(pdg), P, K, float(M), ptr(gamma), ptr(invstd), ptr(dgamma), ptr(dbeta),
+             ptr(ca), ptr(cb), ptr(cc), stream())
+    else:
+        slab = _sync_slab(pdb, pdg, P, K, M, sync, ca.device)
+        call('dmy_bn_sync_bwd_finalize', ptr(slab), sync[1], sync[2], K, ptr(gamma), ptr(invstd), ptr(dgamma),
+             ptr(dbeta), ptr(ca), ptr(cb), ptr(cc), stream())
 
 
 def _defer_affine(z, stats, act, K):
@@ -493,10 +559,11 @@ def _act_pass(g, z, scale, shift, spec, res, rps, out, yps, emit_ok, spd=False):
     return y
 
 
-def _save_ctx(ctx, saved, g, spec, train_bn, bnlink, weight, bias, gamma, beta, has_res, xsink, rsink, spd=False):
+def _save_ctx(ctx, saved, g, spec, train_bn, bnlink, weight, bias, gamma, beta, has_res, xsink, rsink, spd=False,
+              sync=None):
     """everything ConvBNActFn.backward reads, set in this one place"""
     ctx.save_for_backward(*saved)
-    ctx.g, ctx.spec, ctx.train_bn, ctx.bnlink, ctx.spd = g, spec, train_bn, bnlink, spd
+    ctx.g, ctx.spec, ctx.train_bn, ctx.bnlink, ctx.spd, ctx.sync = g, spec, train_bn, bnlink, spd, sync
     ctx.has_bias, ctx.has_res, ctx.xsink, ctx.rsink = bias is not None, has_res, xsink, rsink
     ctx.arena, ctx.wkey = WgradArena.current, weight.data_ptr()
     ctx.pkeys = tuple(t.data_ptr() if t is not None else None for t in (bias, gamma, beta))
@@ -544,8 +611,7 @@ def _bn_bwd_coef(ctx, dt, dy, dps, z, stats, gamma):
              ptr(pdg), stream())
     pdb, pdg, P = _fold_partials(pdb, pdg, P, K, dev)
     dgamma, dbeta = _pgrad(ctx, 1, K, dev), _pgrad(ctx, 2, K, dev)
-    call('dmy_bn_bwd_finalize', ptr(pdb), ptr(pdg), P, K, float(M), ptr(gamma), ptr(stats[3]), ptr(dgamma), ptr(dbeta),
-         ptr(ca), ptr(cb), ptr(cc), stream())
+    _bn_bwd_finalize(pdb, pdg, P, K, M, gamma, stats[3], dgamma, dbeta, ca, cb, cc, ctx.sync)
     return ca, cb, cc, dgamma, dbeta
 
 
@@ -676,6 +742,7 @@ class ConvBNActFn(torch.autograd.Function):
         bn = spec.bn
         train_bn = bn is not None and (bn.training or not bn.track_running_stats)
         infer = not need_grad and not train_bn
+        sync = _bn_sync(bn, train_bn)  # raises under graph capture, ahead of this layer's first launch
         x, g, wf, wt, wkey = _conv_operands(x, weight, spec, need_grad, infer)
         f8 = _conv_fp8(x, g, weight, spec, wkey, f8in, prod, infer)
         res, rps = pixel_stride(res) if res is not None else (None, 0)
@@ -694,7 +761,7 @@ class ConvBNActFn(torch.autograd.Function):
                           False, spd) if act_pass else z
             saved = (x, wt, z)
         else:
-            stats = _conv_bn_stats(x, g, wf, bias, z, bn, train_bn, f8)
+            stats = _conv_bn_stats(x, g, wf, bias, z, bn, train_bn, f8, sync)
             saved = (x, wt, z, *stats, bn.weight)
             if (spec.defer and DEFER_AFFINE[0] and train_bn and need_grad and x.dtype == torch.bfloat16 and
                     spec.act == ACT_NONE and res is None and out is None and g.K % 8 == 0 and f8 is None and
@@ -704,7 +771,8 @@ class ConvBNActFn(torch.autograd.Function):
                 y = _act_pass(g, z, stats[0], stats[1], spec, res, rps, out, yps, True, spd)
                 if x.dtype == torch.bfloat16 and g.K % 128 == 0 and train_bn and not spd:
                     y._dmy_prod = spec  # an fp8 consumer may ask this layer to emit its e4m3 copy (F8Emit)
-        _save_ctx(ctx, saved, g, spec, train_bn, link, weight, bias, gamma, beta, res is not None, xsink, rsink, spd)
+        _save_ctx(ctx, saved, g, spec, train_bn, link, weight, bias, gamma, beta, res is not None, xsink, rsink, spd,
+                  sync)
         return y
 
     @staticmethod

@@ -4,13 +4,13 @@ import torch
 
 from .._lib import call, ptr, stream, ACT_NONE
 from ._base import VW, const_vec, dcode, f32, new_act, out_or_new, vec_ok, vec_view
-from .conv import _bn_finalize, _conv_operands, _conv_wgrad, _dgrad, _dw_check, _fold_partials, _launch_conv_fwd, \
-    _param_spec, _pgrad, _save_ctx, eval_coef
+from .conv import _bn_bwd_finalize, _bn_finalize, _bn_sync, _conv_operands, _conv_wgrad, _dgrad, _dw_check, \
+    _fold_partials, _launch_conv_fwd, _param_spec, _pgrad, _save_ctx, eval_coef
 from .sinks import pass_or_self
 from .timer import KernelTimer
 
 
-def _actbn_stats(z, g, spec, bn, train_bn):
+def _actbn_stats(z, g, spec, bn, train_bn, sync=None):
     """BN coefficients over a = act(z) -> (scale, shift, mean, invstd).  Train mode: dmy_actbn_stats' partial rows,
     folded and finalized by the unchanged dmy_bn_finalize (which also updates the running statistics); eval-mode BN
     under autograd: scale / shift from the running statistics, mean / invstd unused (zero / one)."""
@@ -25,7 +25,7 @@ def _actbn_stats(z, g, spec, bn, train_bn):
     psum, psq = f32(P * K, dev), f32(P * K, dev)
     call('dmy_actbn_stats', dcode(z), ptr(z), K, spec.act, M, K, ptr(psum), ptr(psq), stream())
     psum, psq, P = _fold_partials(psum, psq, P, K, dev)
-    _bn_finalize(psum, psq, P, K, M, bn, mean, invstd, scale, shift)
+    _bn_finalize(psum, psq, P, K, M, bn, mean, invstd, scale, shift, sync)
     return scale, shift, mean, invstd
 
 
@@ -65,6 +65,7 @@ class ConvActBNFn(torch.autograd.Function):
         bn = spec.bn
         train_bn = bn.training or not bn.track_running_stats
         infer = not need_grad and not train_bn
+        sync = _bn_sync(bn, train_bn)  # raises under graph capture, ahead of this layer's first launch
         x, g, wf, wt, _ = _conv_operands(x, weight, spec, need_grad, infer)
         if g.K % VW[x.dtype] or g.s2d or g.Cp != g.C:
             raise NotImplementedError(f'conv -> act -> BN takes whole 16-byte vectors: output channels multiples of '
@@ -77,11 +78,11 @@ class ConvActBNFn(torch.autograd.Function):
             return _actbn_infer(x, g, wf, bias, spec, res, rps, y, yps)
         z = new_act(g.N, g.K, g.OH, g.OW, x)
         _launch_conv_fwd(x, g, wf, bias, z, g.K, None, None)
-        scale, shift, mean, invstd = _actbn_stats(z, g, spec, bn, train_bn)
+        scale, shift, mean, invstd = _actbn_stats(z, g, spec, bn, train_bn, sync)
         call('dmy_actbn_fwd', dcode(z), ptr(z), g.K, spec.act, ptr(scale), ptr(shift), ptr(res), rps, ptr(y), yps, g.M,
              g.K, stream())
         _save_ctx(ctx, (x, wt, z, scale, mean, invstd), g, spec, train_bn, None, weight, bias, gamma, beta,
-                  res is not None, xsink, rsink)
+                  res is not None, xsink, rsink, sync=sync)
         return y
 
     @staticmethod
@@ -99,8 +100,7 @@ class ConvActBNFn(torch.autograd.Function):
             pdb, pdg, R = _fold_partials(pdb, pdg, P, K, dev)
             ca, cb, cc = f32(K, dev), f32(K, dev), f32(K, dev)
             dgamma, dbeta = _pgrad(ctx, 1, K, dev), _pgrad(ctx, 2, K, dev)
-            call('dmy_bn_bwd_finalize', ptr(pdb), ptr(pdg), R, K, float(M), ptr(spec.bn.weight), ptr(invstd), ptr(dgamma),
-                 ptr(dbeta), ptr(ca), ptr(cb), ptr(cc), stream())
+            _bn_bwd_finalize(pdb, pdg, R, K, M, spec.bn.weight, invstd, dgamma, dbeta, ca, cb, cc, ctx.sync)
         else:  # eval-mode BN is a fixed affine map
             ca, cb = scale, const_vec(K, 0.0, dev)
             cc = cb

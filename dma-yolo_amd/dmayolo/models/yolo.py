@@ -542,7 +542,7 @@ def parse_model(d, ch):
             if m in rep_mods:
                 args.insert(2, n)
                 n = 1
-        elif m is nn.BatchNorm2d:
+        elif m is nn.BatchNorm2d:  # YAML-level; SyncBatchNorm only ever comes from converting the built model
             args = [ch[f]]
         elif m in (C.Concat, C.AdConcat2, C.AdConcat3):
             c2 = sum(ch[x] for x in f)

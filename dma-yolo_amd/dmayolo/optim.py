@@ -262,14 +262,16 @@ def ema_update(ema_tensors, model_tensors, d):
 
 def param_groups(model):
     """train.py:197-214 grouping: g0 BN weights (no decay), g1 weights + AdConcat.w / Adapt_Add.w (decay), g2 biases.
-    (relative_position_bias_table and other non-weight/bias params are NOT collected, as in the reference.)"""
+    (relative_position_bias_table and other non-weight/bias params are NOT collected, as in the reference.)
+    The reference groups before it converts to SyncBatchNorm (train.py:272-275), and the conversion keeps the parameter
+    objects: a model converted first must therefore group the same way."""
     import torch.nn as nn
     from .models.common import AdConcat2, AdConcat3, Adapt_Add2, Adapt_Add3
     g0, g1, g2 = [], [], []
     for v in model.modules():
         if hasattr(v, 'bias') and isinstance(v.bias, nn.Parameter):
             g2.append(v.bias)
-        if isinstance(v, nn.BatchNorm2d):
+        if isinstance(v, (nn.BatchNorm2d, nn.SyncBatchNorm)):  # --sync-bn: still no decay
             g0.append(v.weight)
         elif hasattr(v, 'weight') and isinstance(v.weight, nn.Parameter):
             g1.append(v.weight)

@@ -35,7 +35,9 @@ def copy_attr(a, b, include=(), exclude=()):
 
 
 def initialize_weights(model):
-    """utils/torch_utils.py:161-170: BN eps 1e-3, momentum 0.03 on exact-type BatchNorm2d."""
+    """utils/torch_utils.py:161-170: BN eps 1e-3, momentum 0.03 on exact-type BatchNorm2d.  A SyncBatchNorm is left as
+    it is, as in the reference: Model.__init__ runs this before train.py:272-275 converts, and the conversion carries
+    eps and momentum over."""
     for m in model.modules():
         t = type(m)
         if t is nn.BatchNorm2d:
@@ -43,6 +45,18 @@ def initialize_weights(model):
             m.momentum = 0.03
         elif t in (nn.Hardswish, nn.LeakyReLU, nn.ReLU, nn.ReLU6, nn.SiLU):
             m.inplace = True
+
+
+def convert_sync_batchnorm(model, process_group=None):
+    """train.py:272-275 (--sync-bn): torch.nn.SyncBatchNorm.convert_sync_batchnorm(model), after which every train-mode
+    Conv-BN layer takes its batch statistics over all ranks of `process_group` (functional.conv._bn_sync).  Call it on
+    the bare model, before the DDP / ArenaDDP wrap and before the Trainer is built.  The parameters and buffers stay
+    the same tensors under the same state-dict keys, so checkpoints load both ways; the conv specs and inference caches
+    that still point at a replaced BatchNorm2d are dropped.  Returns the converted model."""
+    from ..functional import drop_specs
+    model = nn.SyncBatchNorm.convert_sync_batchnorm(model, process_group)
+    drop_specs(model)
+    return model
 
 
 @torch.no_grad()

@@ -291,6 +291,27 @@ int dmy_reduce_rows(const float* part, int P, int C, float* out, int accumulate,
 int dmy_bn_reduce_rows(int dtype, const void* z, long zps, const void* dy, long dps, long M, int C);
 int dmy_colsum2_rows(long P);
 int dmy_colsum2(const float* a, const float* b, long P, int C, float* oa, float* ob, void* stream);
+/* SyncBatchNorm (torch.nn.SyncBatchNorm, train.py:272-275).  One layer's per-rank sums travel in a slab [R][2C + 1]
+ * of doubles, R = world size: slot r = (sum a[C], sum b[C], n) of rank r, (sum x, sum x^2, pixels) in the forward and
+ * (sum dy, sum dy * xhat, pixels) in the backward.  Every rank packs its own slot and zeros the others, the caller
+ * all-reduces (SUM) the slab -- adding zeros is exact, so the result is an all-gather whatever the collective's order --
+ * and finalizes.  No atomics: bit-identical on every rank and from run to run.  A bad slab / R / rank / C returns
+ * hipErrorInvalidValue and launches nothing.
+ * dmy_bn_sync_pack: column sums of P partial rows of pa / pb [P][C] in double, in dmy_bn_finalize's order, and `count`
+ * into slot `rank`; zeros in every other slot, same launch. */
+int dmy_bn_sync_pack(const float* pa, const float* pb, int P, int C, double count, double* slab, int R, int rank,
+                     void* stream);
+/* What dmy_bn_finalize writes (running statistics with the unbiased variance, num_batches_tracked += 1 when `update`),
+ * from the R slots added in rank order; the global count is read from the slab on the device.  R = 1 equals
+ * dmy_bn_finalize over the same rows bit for bit. */
+int dmy_bn_sync_finalize(const double* slab, int R, int C, const float* gamma, const float* beta, float* running_mean,
+                         float* running_var, long long* num_batches_tracked, float momentum, float eps, int update,
+                         float* mean, float* invstd, float* scale, float* shift, void* stream);
+/* dmy_bn_bwd_finalize over the slab: dgamma / dbeta (nullable) from slot `rank` alone -- parameter gradients stay local
+ * and the DDP reducer averages them, torch's SyncBatchNorm rule -- ca / cb / cc from all slots in rank order over the
+ * global count. */
+int dmy_bn_sync_bwd_finalize(const double* slab, int R, int rank, int C, const float* gamma, const float* invstd,
+                             float* dgamma, float* dbeta, float* ca, float* cb, float* cc, void* stream);
 
 /* ---- SPD-mix downsamplers (csrc/spd.hip): DMConv / DMMConv / DMMConv2 with SM and MP (models/common.py:1460-1475,
  *      1508-1547).  Streaming NHWC kernels, fp32 arithmetic, no atomics.  Supported: bf16 with every channel count and
